@@ -9,10 +9,12 @@ gaussian_renderer.render() + loss.backward() exercise. N > 1: one process per GP
 shards by scene) plus the only exchange the sharded training has: an all-reduce of the shared
 appearance-MLP gradient bucket (24 966 floats). Weak scaling: value = sum of Gaussians over ranks / max time.
 
-Prints ONE JSON line (rank 0). `roofline` describes the dominant kernel (HIP events recorded by the
-library on its launch stream during the timed region); `roofline_step` the whole step with SURVEY 8d's
-algorithmic byte count. `cpu_baseline` times the PyTorch CPU restatement of the render path (the
-reference has no CPU path) on a bounded sample, next to the C/OpenMP oracle. Only that leg touches oracle/.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the headline; everything
+else is measured with --full only: `roofline` describes the dominant kernel (HIP events recorded by the library on its
+launch stream during the timed region); `roofline_step` the whole step with SURVEY 8d's algorithmic byte count.
+`cpu_baseline` times the PyTorch CPU restatement of the render path (the reference has no CPU path) on a
+bounded sample, next to the C/OpenMP oracle. Only that leg touches oracle/. --dump-outputs DIR writes what the last timed
+step computed, so that two builds can be compared output for output on identical (seeded) inputs.
 """
 import argparse
 import json
@@ -31,6 +33,9 @@ HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec (MI355X_MICROARCH.md); measured 
 VALU_PEAK_TFLOPS = 157.3    # MI355X FP32 vector peak (MI355X_MICROARCH.md): 256 CUs x 128 lanes x 2 FLOP x 2.4 GHz
 FP32_PEAK_TFLOPS = 157.3
 APPEARANCE_MLP_FLOATS = 24966  # shared parameters all-reduced per step (scene/gaussian_model.py:52-58)
+DUMP_BYTES = 62 * 10**6        # --dump-outputs: array bytes written at most (the files stay under 64 MB with their headers)
+DUMP_PIXELS = 1 << 21          # per-pixel arrays above this many pixels are sampled (1920x1080 is written whole)
+DUMP_ROWS = 1 << 18            # per-Gaussian arrays: at most this many rows
 
 
 def pick_backend(world, device_count, env):
@@ -93,8 +98,9 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--settle-steps", type=int, default=40,
-                    help="untimed steps between the warm-up's bookkeeping (which idles the GPU for a few ms) and the timed "
-                         "region: the timed steps start from the sustained clock state a training loop runs at")
+                    help="--full: untimed steps between the warm-up's bookkeeping (which idles the GPU for a few ms) and the "
+                         "timed region: the timed steps start from the sustained clock state a training loop runs at (a plain "
+                         "run has no such bookkeeping and goes from the warm-up straight into the timed steps)")
     ap.add_argument("--prewarm-steps", type=int, default=50,
                     help="untimed steps BEFORE the W warm-up steps (the same count on every rank): the device needs ~30 ms of "
                          "sustained load to reach its sustained clock state (tools/diag_ramp.py: 1.35 -> 1.25 ms/step over "
@@ -102,7 +108,7 @@ def main():
     ap.add_argument("--n", type=int, default=0)
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="0 = skip the CPU-baseline leg; otherwise it runs on the workload's own N (a bounded tile sample, ~30-60 s)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: 0 = skip the CPU-baseline leg; otherwise it runs on the workload's own N (a bounded tile sample, ~30-60 s)")
     ap.add_argument("--forward-only", action="store_true", help="report render FPS instead of train-step Gaussians/s")
     ap.add_argument("--d2h-async", action="store_true", help="with --forward-only: download every frame through sfgs.video.FrameDownloader (pinned ring, side stream; informational)")
     ap.add_argument("--d2h-copy", action="store_true", help="with --forward-only: copy every frame to the host like render_video.py:181 (informational; never the headline value)")
@@ -124,7 +130,7 @@ def main():
                          "(gaussian_renderer/__init__.py:37-38) -- the shape the reference actually calls; 'none' (the "
                          "headline of rounds 1-4): no tensor")
     ap.add_argument("--cameras", type=int, default=8,
-                    help="after the timed region (never inside it): K seeded cameras around the headline view, visited in turn "
+                    help="--full, after the timed region (never inside it): K seeded cameras around the headline view, visited in turn "
                          "with a FRESH settings tuple per step whose viewmatrix is a transposed (non-contiguous) view and whose "
                          "subpixel_offset is a newly allocated zeros tensor -- what gaussian_renderer.render() builds on every "
                          "call (gaussian_renderer/__init__.py:37-55, scene/cameras.py:62); reported as `train_shaped`. 0 = skip")
@@ -139,10 +145,21 @@ def main():
     ap.add_argument("--pin-below", type=int, default=500_000, help="the size below which --pin-cores applies (released above 1.6 x this)")
     ap.add_argument("--cpu-leg", default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-only", action="store_true", help="run only the CPU-baseline legs and print them")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the box probe, the per-kernel split and the rooflines, the host-bound "
+                         "check, the training-shaped line (--cameras), cfg3's render phase, the all-reduce time and the CPU "
+                         "baseline (--cpu-sample). Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the "
+                         "rasterizer's color, depth, alpha and radii and, unless --forward-only, the gradients of its inputs "
+                         "(grad_<input>); per-pixel arrays above 2^21 pixels and per-Gaussian arrays above 2^18 rows (or the "
+                         "64 MB budget) as a fixed seeded sample of pixels / Gaussians. Rank 0 only")
     argv = sys.argv[1:]
     if not argv and "RANK" in os.environ and os.environ.get("SFGS_BENCH_ARGV"):
         argv = json.loads(os.environ["SFGS_BENCH_ARGV"])   # a rank spawned by `python bench.py --gpus N ...` (see below)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     CFG = {"cfg2": dict(n=2_000_000, width=1920, height=1080, zrange=(250.0, 350.0), configs_index=1),
            "cfg3": dict(n=2_000_000, width=1024, height=1024, zrange=(250.0, 350.0), configs_index=2),
            "cfg4": dict(n=5_000_000, width=2560, height=1440, zrange=(500.0, 700.0), configs_index=3)}[args.config]
@@ -155,9 +172,10 @@ def main():
         return
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU
-        # (the driver's own multi-GPU invocation already comes through torchrun and skips this)
+        # `python bench.py --gpus N` without a launcher: run under torch.distributed.run in a child process, one rank per
+        # GPU (the driver's own multi-GPU invocation already comes through torchrun and skips this)
         import socket
+        import subprocess
         s_ = socket.socket()
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
@@ -166,9 +184,10 @@ def main():
         # this process's arguments travel in the environment: torchrun's own parser rejects script options that are
         # prefixes of its options ("--n" is ambiguous between --nnodes, --nproc-per-node, ...) even behind the script name
         os.environ["SFGS_BENCH_ARGV"] = json.dumps(sys.argv[1:])
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                   f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port",
-                                   str(port), os.path.abspath(__file__)])
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+                              f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port",
+                              str(port), os.path.abspath(__file__)])
+        sys.exit(rc if rc >= 0 else 128 - rc)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -228,7 +247,9 @@ def main():
         from sfgs.video import FrameDownloader
         downloader = FrameDownloader(depth=3, device=dev)
 
-    def step(forward_only=args.forward_only):
+    last = {}   # keep=True: the outputs of that step, for --dump-outputs (its gradients stay in .grad)
+
+    def step(forward_only=args.forward_only, keep=False):
         if forward_only:
             with torch.no_grad():
                 out = rast(means3D=t["means3D"], means2D=means2D, shs=t["shs"], colors_precomp=t["colors_precomp"],
@@ -237,13 +258,17 @@ def main():
                     out[0].cpu()   # rendering.cpu() of the reference's video loop: a synchronous 24.9 MB PCIe copy at 1080p
                 elif args.d2h_async:
                     downloader.submit(out[0])
+            if keep:
+                last["out"] = out
             return
         for v in list(t.values()) + [means2D]:
             if v is not None:
                 v.grad = None
-        color, depth, _, _, _, _ = rast(means3D=t["means3D"], means2D=means2D, shs=t["shs"],
-                                        colors_precomp=t["colors_precomp"], opacities=t["opacities"],
-                                        scales=t["scales"], rotations=t["rotations"])
+        out = rast(means3D=t["means3D"], means2D=means2D, shs=t["shs"], colors_precomp=t["colors_precomp"],
+                   opacities=t["opacities"], scales=t["scales"], rotations=t["rotations"])
+        if keep:
+            last["out"] = out
+        color, depth = out[0], out[1]
         torch.autograd.backward([color, depth], [gc, gd])
         if dist is not None:
             if ar_events is not None:
@@ -263,23 +288,24 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # Warm-up with every kernel timed (HIP events on the launch stream): gives the per-kernel split and names the
-    # dominant kernel. The timed region then brackets ONLY that kernel (each event pair costs the GPU ~4 us of
-    # bubble; 9 kernels x 2 events per step would inflate the step by ~5 %).
-    # one untimed frame with the diagnostic counter read (full stream sync) for max_tile_list; the timed steps use
-    # the default mid-frame read
-    collect_full_counters(True)
-    step()
-    max_tile_list = last_counters()["max_tile_list"]
-    collect_full_counters(False)
-    box = box_probe(dev, L) if rank == 0 else None
+    max_tile_list = box = idu = allreduce_ms = None
+    if args.full:
+        # Warm-up with every kernel timed (HIP events on the launch stream): gives the per-kernel split and names the
+        # dominant kernel. The timed region then brackets ONLY that kernel (each event pair costs the GPU ~4 us of
+        # bubble; 9 kernels x 2 events per step would inflate the step by ~5 %).
+        # one untimed frame with the diagnostic counter read (full stream sync) for max_tile_list; the timed steps use
+        # the default mid-frame read
+        collect_full_counters(True)
+        step()
+        max_tile_list = last_counters()["max_tile_list"]
+        collect_full_counters(False)
+        box = box_probe(dev, L) if rank == 0 else None
     # device clock ramp (power management, not this code: the same ramp follows every idle period): a training loop runs
     # at the sustained state, so bring the device there before the W warm-up and K timed steps
     for _ in range(max(args.prewarm_steps, 0)):   # a fixed count: with N > 1 every step holds a collective
         step()
     torch.cuda.synchronize(dev)
-    idu = None
-    if args.config == "cfg3" and not args.forward_only:
+    if args.full and args.config == "cfg3" and not args.forward_only:
         # the IDU episode's render phase (train.py:360-525: 108 pseudo-camera renders under no_grad), then the training steps
         n_idu = 108
         for _ in range(5):
@@ -294,61 +320,70 @@ def main():
                "what": "108 forward-only 1024x1024 renders (no_grad, no D2H copy) before the timed fwd+bwd steps"}
         for _ in range(10):
             step()
-    L.profile_select(None)
-    n_prof = max(args.warmup - 1, 1) if args.warmup else 0   # the first step sizes the scratch (may re-plan): not timed
-    for i in range(args.warmup):
-        if i == args.warmup - n_prof:
-            fence()
-            L.profile_enable(True)
-            ar_events = [] if dist is not None else None
-        step()
-    fence()
-    allreduce_ms = None
-    if ar_events:
-        allreduce_ms = sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)
-    ar_events = None
-    # every bracketed launch carries the cost of its own event pair: measure it (empty pairs on the same stream). The
-    # per-kernel figures reported below are the RAW event times (they agree with rocprofv3's kernel trace to ~1 %, VERDICT
-    # r4: the subtraction over-corrected by 3 %); only `gpu_busy_ms_per_step` takes the pairs' cost out, so that it stays
-    # comparable with the un-bracketed step time
-    cal = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
-    for a_, b_ in cal:
-        a_.record(); b_.record()
-    torch.cuda.synchronize(dev)
-    event_pair_ms = sorted(a_.elapsed_time(b_) for a_, b_ in cal)[len(cal) // 2]
-    warm_prof = L.profile_collect() if args.warmup else {}
-    L.profile_enable(True)
+    if args.full:
+        L.profile_select(None)
+        n_prof = max(args.warmup - 1, 1) if args.warmup else 0   # the first step sizes the scratch (may re-plan): not timed
+        for i in range(args.warmup):
+            if i == args.warmup - n_prof:
+                fence()
+                L.profile_enable(True)
+                ar_events = [] if dist is not None else None
+            step()
+        fence()
+        allreduce_ms = None
+        if ar_events:
+            allreduce_ms = sum(a.elapsed_time(b) for a, b in ar_events) / len(ar_events)
+        ar_events = None
+        # every bracketed launch carries the cost of its own event pair: measure it (empty pairs on the same stream). The
+        # per-kernel figures reported below are the RAW event times (they agree with rocprofv3's kernel trace to ~1 %, VERDICT
+        # r4: the subtraction over-corrected by 3 %); only `gpu_busy_ms_per_step` takes the pairs' cost out, so that it stays
+        # comparable with the un-bracketed step time
+        cal = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
+        for a_, b_ in cal:
+            a_.record(); b_.record()
+        torch.cuda.synchronize(dev)
+        event_pair_ms = sorted(a_.elapsed_time(b_) for a_, b_ in cal)[len(cal) // 2]
+        warm_prof = L.profile_collect() if args.warmup else {}
+        L.profile_enable(True)
 
-    def group(prof, nsteps):
-        out = {}
-        for name, (ms, launches) in prof.items():
-            key = "sort_tiles" if name.startswith("sort_tiles") else name
-            e = out.setdefault(key, {"ms_per_step": 0.0, "launches": 0})
-            e["ms_per_step"] += ms / max(nsteps, 1)
-            e["launches"] += launches
-        return out
-    warm = group(warm_prof, n_prof)
-    dom = max(warm, key=lambda k: warm[k]["ms_per_step"]) if warm else None
-    dom_names = [n for n in warm_prof if (n.startswith("sort_tiles") and dom == "sort_tiles") or n == dom]
-    L.profile_select(dom_names if dom_names else None)
-    # The bookkeeping above (event calibration, reading the warm-up's events back) leaves the GPU idle for a few
-    # milliseconds, and the device's power management answers idle time with a clock ramp that lasts ~30 steps
-    # (tools/diag_transient.py: after 20 ms of idle the next steps take 1.23, 1.14, 1.09, 1.07 ms per ten, 1.065 without
-    # the idle). A training loop never idles like that, so run a fixed number of untimed steps again and go from them
-    # STRAIGHT into the bracketing barrier + synchronize and the K timed steps.
-    L.profile_enable(False)
-    for _ in range(max(args.settle_steps, 0)):
-        step()
-    L.profile_enable(True)
-    fence()
+        def group(prof, nsteps):
+            out = {}
+            for name, (ms, launches) in prof.items():
+                key = "sort_tiles" if name.startswith("sort_tiles") else name
+                e = out.setdefault(key, {"ms_per_step": 0.0, "launches": 0})
+                e["ms_per_step"] += ms / max(nsteps, 1)
+                e["launches"] += launches
+            return out
+        warm = group(warm_prof, n_prof)
+        dom = max(warm, key=lambda k: warm[k]["ms_per_step"]) if warm else None
+        dom_names = [n for n in warm_prof if (n.startswith("sort_tiles") and dom == "sort_tiles") or n == dom]
+        L.profile_select(dom_names if dom_names else None)
+        # The bookkeeping above (event calibration, reading the warm-up's events back) leaves the GPU idle for a few
+        # milliseconds, and the device's power management answers idle time with a clock ramp that lasts ~30 steps
+        # (tools/diag_transient.py: after 20 ms of idle the next steps take 1.23, 1.14, 1.09, 1.07 ms per ten, 1.065 without
+        # the idle). A training loop never idles like that, so run a fixed number of untimed steps again and go from them
+        # STRAIGHT into the bracketing barrier + synchronize and the K timed steps.
+        L.profile_enable(False)
+        for _ in range(max(args.settle_steps, 0)):
+            step()
+        L.profile_enable(True)
+        fence()
+    else:
+        for _ in range(args.warmup):
+            step()
+        fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=i == args.steps - 1)
     fence()
     elapsed = time.perf_counter() - t0
-    prof = L.profile_collect()
-    L.profile_enable(False)
-    L.profile_select(None)
+    if args.full:
+        prof = L.profile_collect()
+        L.profile_enable(False)
+        L.profile_select(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"], t, means2D, H, W)
+    last.clear()
     # Is the HOST ever the bottleneck? After the timed region (never inside it), SPAN_STEPS more steps with ONE event in front
     # of and one behind every step on the launch stream and no per-kernel bracket: `gpu_span` = first launch .. last kernel of
     # a step, `gpu_gap_between_steps` = end of a step .. start of the next. While the host runs ahead the gap is the cost of
@@ -356,7 +391,7 @@ def main():
     # each carries a few us of event overhead, and their sum is not the step -- rocprofv3's kernel trace of the headline shows
     # the kernels back to back: 940.6 us of kernels in a 942.4 us step, profiles/r5_v1_rocprofv3_100steps.txt.)
     span = None
-    if not args.forward_only:
+    if args.full and not args.forward_only:
         SPAN_STEPS = 20
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(SPAN_STEPS)]
         for a_, b_ in evs:
@@ -372,7 +407,7 @@ def main():
                         "stream; a gap above the cost of two event records (~0.01 ms) means the GPU waited for the host"}
 
     train_shaped = None
-    if args.cameras > 0 and not args.forward_only and dist is None:   # single-process runs only: its steps hold no collective
+    if args.full and args.cameras > 0 and not args.forward_only and dist is None:   # single-process runs only: its steps hold no collective
         train_shaped = run_train_shaped(args, dev, frame, t, means2D, gc, gd, W, H, max(sh, 0), GaussianRasterizationSettings,
                                         GaussianRasterizer, last_counters, step)
     per_rank_ms = [elapsed / args.steps * 1e3]
@@ -411,81 +446,83 @@ def main():
         unit = "Gaussians/s"
         value = world * N / (ms_step * 1e-3)
 
-    # per-kernel view (rank 0's launches): dominant kernel from the timed region, the split from the warm-up steps
-    kb = kernel_bytes(N, Nvis, D_ref, P)
-    per_kernel = dict(warm)
-    timed = group(prof, args.steps)
-    if dom in timed:
-        per_kernel[dom] = timed[dom]
-    # HBM traffic of the dominant kernel from the rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE: separate runs,
-    # gfx950 FETCH_SIZE x2 correction per MI355X_MICROARCH.md) of THIS workload, committed under profiles/ by
-    # tools/collect_profiles.sh. bench.py cannot collect PMCs on itself; null when the workload differs.
-    traffic, traffic_source = load_traffic(N, W, H, args.forward_only)
-    roofline = None
-    if dom is not None:
-        dur = per_kernel[dom]["ms_per_step"] * 1e-3
-        ach = kb.get(dom, 0) / dur / 1e9
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic.get(dom),
-                    "traffic_source": traffic_source if traffic.get(dom) is not None else None,
-                    "avg_launch_ms": round(per_kernel[dom]["ms_per_step"], 4),
-                    "algorithmic_bytes_per_launch": int(kb.get(dom, 0))}
-        if dom.startswith("composite"):
-            # SURVEY 8(d)'s second line for the compositing kernels, which are VALU- not HBM-bound: every binned
-            # (Gaussian, 8x8 tile) pair is evaluated on the wave's 64 pixel lanes; 22 FLOP per (pixel, splat)
-            # evaluation is SURVEY's count for the forward blend (the backward does ~2.5x that, not credited)
-            pairs = 64 * D_eff
-            tf = pairs * 22 / dur / 1e12
-            roofline["valu"] = {"pair_evaluations_per_launch": int(pairs), "flop_per_pair": 22,
-                                "achieved": round(tf, 2), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                "frac": round(tf / VALU_PEAK_TFLOPS, 4)}
-    # north_star states its target on the forward + backward COMPOSITE pair: the two kernels' algorithmic bytes over the
-    # sum of their launch durations (the forward's from the warm-up steps' bracketing, see kernel_ms_source)
-    roofline_pair = None
-    if not args.forward_only and "composite_fwd" in per_kernel and "composite_bwd" in per_kernel:
-        pair_bytes = kb.get("composite_fwd", 0) + kb.get("composite_bwd", 0)
-        pair_ms = per_kernel["composite_fwd"]["ms_per_step"] + per_kernel["composite_bwd"]["ms_per_step"]
-        pa = pair_bytes / (pair_ms * 1e-3) / 1e9
-        roofline_pair = {"kernels": ["composite_fwd", "composite_bwd"], "bound": "hbm", "achieved": round(pa, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(pa / HBM_PEAK_GBS, 5),
-                         "algorithmic_bytes": int(pair_bytes), "ms": round(pair_ms, 4), "target_frac": 0.40}
-    step_ach = B_step / (ms_step * 1e-3) / 1e9
-    roofline_step = {"bound": "hbm", "achieved": round(step_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(step_ach / HBM_PEAK_GBS, 5), "algorithmic_bytes_per_step": int(B_step),
-                     "kernel_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(per_kernel.items())},
-                     "kernel_ms_source": "raw HIP-event brackets on the launch stream (dominant kernel: timed region; others: "
-                                         "warm-up steps, where every kernel is bracketed)",
-                     "event_pair_us": round(event_pair_ms * 1e3, 2),
-                     "gpu_busy_ms_per_step": round(sum(max(v["ms_per_step"] - event_pair_ms * v["launches"] / max(
-                         args.steps if k == dom else n_prof, 1), 0.0) for k, v in per_kernel.items()), 4),
-                     "gpu_busy_source": "sum of the brackets minus the measured cost of an empty event pair per launch (a LOWER "
-                                        "bound: the subtraction over-corrects; see host_bound for whether the GPU ever waits)",
-                     "host_bound": span}
-    if traffic:
-        # the waste next to the contract's `frac`: real HBM traffic of the whole step from the committed PMC
-        # passes (same file and provenance as roofline.traffic) against the algorithmic bytes
-        # the kernels of a steady-state step (the split route's fine_bin / sort_tiles_reg run in the first, un-hinted frame only)
-        names = ("preprocess", "bin_count", "bin_rank", "bin_scatter", "select_sort", "composite_fwd", "composite_bwd",
-                 "preprocess_bwd", "subpix_bound", "zero_head")
-        tot = sum(v for k, v in traffic.items() if k in names)
-        if tot > 0 and not args.forward_only:
-            roofline_step["traffic"] = int(tot)
-            roofline_step["traffic_over_algorithmic"] = round(tot / B_step, 3)
-            roofline_step["traffic_gbs"] = round(tot / (ms_step * 1e-3) / 1e9, 1)
-            roofline_step["traffic_source"] = traffic_source
+    roofline = roofline_pair = roofline_step = None
+    if args.full:
+        # per-kernel view (rank 0's launches): dominant kernel from the timed region, the split from the warm-up steps
+        kb = kernel_bytes(N, Nvis, D_ref, P)
+        per_kernel = dict(warm)
+        timed = group(prof, args.steps)
+        if dom in timed:
+            per_kernel[dom] = timed[dom]
+        # HBM traffic of the dominant kernel from the rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE: separate runs,
+        # gfx950 FETCH_SIZE x2 correction per MI355X_MICROARCH.md) of THIS workload, committed under profiles/ by
+        # tools/collect_profiles.sh. bench.py cannot collect PMCs on itself; null when the workload differs.
+        traffic, traffic_source = load_traffic(N, W, H, args.forward_only)
+        roofline = None
+        if dom is not None:
+            dur = per_kernel[dom]["ms_per_step"] * 1e-3
+            ach = kb.get(dom, 0) / dur / 1e9
+            roofline = {"kernel": dom, "bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic.get(dom),
+                        "traffic_source": traffic_source if traffic.get(dom) is not None else None,
+                        "avg_launch_ms": round(per_kernel[dom]["ms_per_step"], 4),
+                        "algorithmic_bytes_per_launch": int(kb.get(dom, 0))}
+            if dom.startswith("composite"):
+                # SURVEY 8(d)'s second line for the compositing kernels, which are VALU- not HBM-bound: every binned
+                # (Gaussian, 8x8 tile) pair is evaluated on the wave's 64 pixel lanes; 22 FLOP per (pixel, splat)
+                # evaluation is SURVEY's count for the forward blend (the backward does ~2.5x that, not credited)
+                pairs = 64 * D_eff
+                tf = pairs * 22 / dur / 1e12
+                roofline["valu"] = {"pair_evaluations_per_launch": int(pairs), "flop_per_pair": 22,
+                                    "achieved": round(tf, 2), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                    "frac": round(tf / VALU_PEAK_TFLOPS, 4)}
+        # north_star states its target on the forward + backward COMPOSITE pair: the two kernels' algorithmic bytes over the
+        # sum of their launch durations (the forward's from the warm-up steps' bracketing, see kernel_ms_source)
+        roofline_pair = None
+        if not args.forward_only and "composite_fwd" in per_kernel and "composite_bwd" in per_kernel:
+            pair_bytes = kb.get("composite_fwd", 0) + kb.get("composite_bwd", 0)
+            pair_ms = per_kernel["composite_fwd"]["ms_per_step"] + per_kernel["composite_bwd"]["ms_per_step"]
+            pa = pair_bytes / (pair_ms * 1e-3) / 1e9
+            roofline_pair = {"kernels": ["composite_fwd", "composite_bwd"], "bound": "hbm", "achieved": round(pa, 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(pa / HBM_PEAK_GBS, 5),
+                             "algorithmic_bytes": int(pair_bytes), "ms": round(pair_ms, 4), "target_frac": 0.40}
+        step_ach = B_step / (ms_step * 1e-3) / 1e9
+        roofline_step = {"bound": "hbm", "achieved": round(step_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(step_ach / HBM_PEAK_GBS, 5), "algorithmic_bytes_per_step": int(B_step),
+                         "kernel_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(per_kernel.items())},
+                         "kernel_ms_source": "raw HIP-event brackets on the launch stream (dominant kernel: timed region; others: "
+                                             "warm-up steps, where every kernel is bracketed)",
+                         "event_pair_us": round(event_pair_ms * 1e3, 2),
+                         "gpu_busy_ms_per_step": round(sum(max(v["ms_per_step"] - event_pair_ms * v["launches"] / max(
+                             args.steps if k == dom else n_prof, 1), 0.0) for k, v in per_kernel.items()), 4),
+                         "gpu_busy_source": "sum of the brackets minus the measured cost of an empty event pair per launch (a LOWER "
+                                            "bound: the subtraction over-corrects; see host_bound for whether the GPU ever waits)",
+                         "host_bound": span}
+        if traffic:
+            # the waste next to the contract's `frac`: real HBM traffic of the whole step from the committed PMC
+            # passes (same file and provenance as roofline.traffic) against the algorithmic bytes
+            # the kernels of a steady-state step (the split route's fine_bin / sort_tiles_reg run in the first, un-hinted frame only)
+            names = ("preprocess", "bin_count", "bin_rank", "bin_scatter", "select_sort", "composite_fwd", "composite_bwd",
+                     "preprocess_bwd", "subpix_bound", "zero_head")
+            tot = sum(v for k, v in traffic.items() if k in names)
+            if tot > 0 and not args.forward_only:
+                roofline_step["traffic"] = int(tot)
+                roofline_step["traffic_over_algorithmic"] = round(tot / B_step, 3)
+                roofline_step["traffic_gbs"] = round(tot / (ms_step * 1e-3) / 1e9, 1)
+                roofline_step["traffic_source"] = traffic_source
 
     host.update(affinity.state())   # what the timed region ran under
     affinity.auto(cores=0)
     affinity.unpin()   # (the CPU legs use every host core)
     cpu_baseline = None
-    if rank == 0 and args.gpus == 1 and args.cpu_sample != 0 and not args.forward_only and args.config == "cfg2":
+    if args.full and rank == 0 and args.gpus == 1 and args.cpu_sample != 0 and not args.forward_only and args.config == "cfg2":
         cpu_baseline = run_cpu_baseline(N, W, H)
 
     if rank == 0:
         out = {
             "metric": metric, "value": value, "unit": unit, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"configs[{CFG['configs_index']}]: synthetic {args.config} scene (SURVEY 8d), N={N} Gaussians/GPU, "
                                    f"{W}x{H}, z ~ U({zrange[0]:g}, {zrange[1]:g}), "
                                    f"{'colors_precomp' if sh < 0 else 'SH degree %d in-kernel' % sh}, "
@@ -495,7 +532,8 @@ def main():
                        "N": N, "width": W, "height": H, "N_vis": Nvis, "D_ref_16x16": D_ref, "D_binned_8x8": D_eff,
                        "max_tile_list": max_tile_list, "parallelism": f"scene-per-gpu x{world}",
                        "collective_backend": backend if dist is not None else None,
-                       "prewarm_steps": args.prewarm_steps, "settle_steps": args.settle_steps, "order": args.order},
+                       "prewarm_steps": args.prewarm_steps, "settle_steps": args.settle_steps if args.full else 0,
+                       "order": args.order},
             "subpixel_offset": args.subpixel_offset, "kernel_ms_brackets": "raw",   # not comparable with r1-r4 lines otherwise
             "box": box, "host": host,
             "train_shaped": train_shaped,
@@ -519,6 +557,41 @@ def main():
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(outdir, out, params, means2D, H, W):
+    """--dump-outputs: what a caller of the timed path received from its last step -- the rasterizer's outputs (`norm` is
+    left out: a constant zero view, nothing computes it) and the gradients autograd left in the inputs' .grad -- as
+    outdir/<name>.npy in float32. Per-pixel arrays ([C,H,W]) above DUMP_PIXELS pixels keep a seeded sample of pixels
+    ([C,DUMP_PIXELS]); per-Gaussian arrays ([N,...]) keep a seeded sample of rows, the same rows in every array, as many as
+    DUMP_ROWS and what DUMP_BYTES leaves after the images allow. The samples depend on N, H, W only."""
+    import numpy as np
+    color, depth, _norm, alpha, radii = out[:5]
+    pixel = {"color": color, "depth": depth, "alpha": alpha}
+    rows = {"radii": radii}
+    for name, v in list(params.items()) + [("means2D", means2D)]:
+        if v is not None and v.grad is not None:
+            rows["grad_" + name] = v.grad
+    arrays = {}
+    P = H * W
+    if P > DUMP_PIXELS:
+        pick = torch.from_numpy(np.sort(np.random.default_rng(1).choice(P, DUMP_PIXELS, replace=False))).to(color.device)
+        pixel = {k: v.reshape(-1, P)[:, pick] for k, v in pixel.items()}
+    arrays.update(pixel)
+    N = radii.shape[0]
+    left = DUMP_BYTES - sum(4 * v.numel() for v in pixel.values())
+    n = min(N, DUMP_ROWS, left // sum(4 * (v.numel() // max(N, 1)) for v in rows.values()))
+    if n < N:
+        pick = torch.from_numpy(np.sort(np.random.default_rng(2).choice(N, n, replace=False))).to(radii.device)
+        rows = {k: v[pick] for k, v in rows.items()}
+    arrays.update(rows)
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        a = v.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    assert total <= DUMP_BYTES, total
 
 
 def run_train_shaped(args, dev, frame, t, means2D, gc, gd, W, H, sh_degree, Settings, Rasterizer, last_counters, headline_step):
@@ -631,13 +704,13 @@ def load_traffic(N, W, H, forward_only):
 def run_cpu_baseline(n, W, H):
     """the reference has no CPU render path (gaussian_renderer/__init__.py:27,38 hard-code "cuda"), so "the
     reference's PyTorch CPU render path" is our PyTorch restatement of the same algorithm (oracle/tiled_torch.py, autograd
-    backward), timed with torch.set_num_threads(all host cores): `value` is for THIS workload, from a bounded sample of
-    its tiles with the extrapolation stated; cfg 1 (BASELINE.json configs[0]) runs in full. The C/OpenMP oracle's time
-    (ours too, a "port") is reported alongside. Reported baselines, not targets. Every leg runs in its own process with a
-    time limit, so a slow host can never take the bench line down."""
+    backward), timed with torch.set_num_threads(the host cores this run may use: OMP_NUM_THREADS where it is set): `value`
+    is for THIS workload, from a bounded sample of its tiles with the extrapolation stated; cfg 1 (BASELINE.json configs[0])
+    runs in full. The C/OpenMP oracle's time (ours too, a "port") is reported alongside. Reported baselines, not targets.
+    Every leg runs in its own process with a time limit, so a slow host can never take the bench line down."""
     import subprocess
     cores = os.cpu_count() or 1
-    threads = int(os.environ.get("SFGS_CPU_THREADS", cores))
+    threads = int(os.environ.get("SFGS_CPU_THREADS", os.environ.get("OMP_NUM_THREADS", cores)))
     out = {"value": None, "unit": "Gaussians/s", "cores": threads, "kind": "pytorch-restatement", "sample": None}
 
     def leg(name, limit):

@@ -61,7 +61,7 @@ def test_shared_grad_bucket_all_reduces_over_rccl_on_the_device():
 def test_bench_force_dist_runs_the_collective_every_step():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--n", "200000",
                         "--width", "640", "--height", "360", "--steps", "5", "--warmup", "3", "--prewarm-steps", "2",
-                        "--cpu-sample", "0"], env=_env(), capture_output=True, text=True, timeout=600)
+                        "--cpu-sample", "0", "--full"], env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["config"]["collective_backend"] == "nccl" and line["n_gpus"] == 1
@@ -78,7 +78,7 @@ def test_bench_two_ranks_emit_the_line_the_scale_parser_reads():
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "200000", "--width", "640",
                         "--height", "360", "--steps", "5", "--warmup", "3", "--prewarm-steps", "2", "--settle-steps", "2",
-                        "--cpu-sample", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--cpu-sample", "0", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines   # rank 0 only
@@ -110,7 +110,7 @@ def test_bench_eight_ranks_on_the_one_gpu():
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--n", "50000", "--width", "480",
                         "--height", "270", "--steps", "4", "--warmup", "2", "--prewarm-steps", "2", "--settle-steps", "2",
-                        "--cpu-sample", "0"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--cpu-sample", "0", "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines

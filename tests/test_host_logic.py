@@ -292,3 +292,44 @@ def test_bench_step_traffic_sums_the_steady_state_kernels():
     for k in ("composite_bwd", "composite_fwd", "preprocess", "preprocess_bwd", "bin_scatter", "select_sort"):
         assert t.get(k, 0) > 0, k
     assert b.load_traffic(1000, 64, 64, False) == ({}, None)
+
+
+def test_bench_dump_outputs_fits_the_budget_and_samples_by_shape_only(tmp_path):
+    """--dump-outputs: float32 files, 64 MB at most; above the caps a seeded sample of pixels (the same in every image) and
+    of Gaussians (the same rows in every per-Gaussian array) that does not depend on the values."""
+    b = _bench_module()
+    N, H, W = 300_000, 1440, 2560                       # more pixels than DUMP_PIXELS, more rows than the budget leaves
+    P = H * W
+
+    def outputs(seed):
+        g = torch.Generator().manual_seed(seed)
+        ramp = torch.arange(P, dtype=torch.float32).reshape(1, H, W)
+        out = (ramp.repeat(3, 1, 1), ramp.clone(), torch.zeros(1).expand(3, H, W), torch.rand(1, H, W, generator=g),
+               torch.arange(N, dtype=torch.int32), None)
+        params = {"means3D": torch.zeros(N, 3), "shs": torch.zeros(N, 16, 3), "colors_precomp": None,
+                  "opacities": torch.zeros(N, 1), "scales": torch.zeros(N, 3), "rotations": torch.zeros(N, 4)}
+        m2 = torch.zeros(N, 3)
+        for v in [p for p in params.values() if p is not None] + [m2]:
+            v.grad = torch.arange(N, dtype=torch.float32).reshape(N, *[1] * (v.dim() - 1)).expand_as(v) + 0.5 * torch.rand(
+                v.shape, generator=g)
+        return out, params, m2
+
+    runs = []
+    for seed, d in ((0, tmp_path / "a"), (1, tmp_path / "b")):
+        b.dump_outputs(str(d), *outputs(seed), H, W)
+        files = sorted(os.listdir(d))
+        assert files == ["alpha.npy", "color.npy", "depth.npy", "grad_means2D.npy", "grad_means3D.npy", "grad_opacities.npy",
+                         "grad_rotations.npy", "grad_scales.npy", "grad_shs.npy", "radii.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10**6
+        z = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in z.values())
+        assert z["color"].shape == (3, b.DUMP_PIXELS) and z["depth"].shape == (1, b.DUMP_PIXELS)
+        px = z["depth"][0]
+        assert np.all(np.diff(px) > 0) and (z["color"] == px).all()          # the same sorted pixels in every image
+        rows = z["radii"]
+        assert 0 < rows.shape[0] < N and np.all(np.diff(rows) > 0)
+        for k, a in z.items():
+            if k.startswith("grad_"):
+                assert a.shape[0] == rows.shape[0] and (np.floor(a.reshape(a.shape[0], -1)) == rows[:, None]).all(), k
+        runs.append((px, rows))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])

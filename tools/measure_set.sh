@@ -6,8 +6,8 @@ TAG=${1:-run}
 cd "${GRAFT_REPO_ROOT:-.}"
 R=$PWD/gpurun_out/meas_$TAG
 mkdir -p "$R"
-B="timeout 300 python bench.py --cpu-sample 0"
-timeout 400 python bench.py > "$R/bench_default.json" 2> "$R/bench_default.err"
+B="timeout 300 python bench.py --full --cpu-sample 0"
+timeout 400 python bench.py --full > "$R/bench_default.json" 2> "$R/bench_default.err"
 $B --n 500000 > "$R/bench_500000.json" 2>/dev/null
 $B --n 1000000 > "$R/bench_1000000.json" 2>/dev/null
 $B --config cfg4 > "$R/bench_cfg4.json" 2>/dev/null          # 5 M, 2560x1440, z ~ U(500, 700), dL/ddepth != 0
