@@ -12,6 +12,7 @@
  *                      diff_gauss.GaussianRasterizationSettings    gaussian_renderer/__init__.py:40-55
  *                      autograd backward of that call              train.py:279,845
  *   sfgs_ssim_*        fused_ssim.fused_ssim(img1, img2)           train.py:42,222,778
+ *   sfgs_loss_*        the loss statements: mask products, l1_loss, fused_ssim, scrub, pearson_corrcoef   train.py:205-234,760-799
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
  *
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 18
+#define SFGS_ABI_VERSION 19
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -387,6 +388,49 @@ int sfgs_ssim_forward(const float* img1, const float* img2, int32_t B, int32_t C
 int sfgs_ssim_backward(const float* img1, const float* img2, int32_t B, int32_t C, int32_t H,
                        int32_t W, const void* scratch, const float* dL_dmean, float* dL_dimg1,
                        void* stream);
+
+/* Fused training loss (ABI 19): the statements between render() and loss.backward() (train.py:205-234; :760-799 in the
+ * IDU episode) as three launches forward and two backward, with no host read of a device value:
+ *   x' = mask * image, y' = mask * gt_image, a = mask * gt_depth, b = mask * depth
+ *   Ll1 = mean |x' - y'|;   ssim = mean SSIM(x', y') (the fused_ssim kernels' arithmetic: bit-identical to the fused_ssim
+ *   value when there is no mask or it is all ones);   r = pearson(a, b) over the pairs the scrub keeps, clamped to [-1, 1]
+ *   (torchmetrics' formula on the centred sums, moments accumulated in float64);   depth_loss = 1 - r;
+ *   loss = (1 - lambda_dssim) * Ll1 + lambda_dssim * (1 - ssim) + lambda_depth * depth_loss.
+ * A pair (a, b) with a non-finite member is scrubbed: SFGS_LOSS_INVALID_ZERO makes it (0, 0) and keeps it in the count
+ * (train.py:229-231), _DROP leaves it out (train.py:788-790; n is counted on the device), _KEEP does not scrub. n = 0 or a
+ * constant member gives NaN (0 / 0), as in torch. Every reduction runs in a fixed order: bit-reproducible run to run.
+ * image, gt_image: [C,H,W] float32. depth, gt_depth: [H*W] float32 (NULL without SFGS_LOSS_DEPTH). mask: NULL
+ * (mask_elems 0), ONE device float (mask_elems 1: Camera.original_mask of a view without a mask) or [H*W].
+ * SFGS_LOSS_L1_STREAM (alone; no mask; invalid_mode _KEEP): Ll1 = mean |gt_depth - depth| over C*H*W elements of two
+ * arbitrary arrays, through the streaming kernels -- the l1_loss drop-in.
+ * out5 / grad_out5: five device floats -- loss, Ll1, ssim, depth_loss, r -- and the gradients arriving at them (terms that
+ * were not asked for are written as 0). The backward needs the forward's scratch and a with_grad != 0 forward for g_image;
+ * g_image [C,H,W], g_depth, g_gt_depth [H*W] may each be NULL (not wanted). */
+#define SFGS_LOSS_PHOTOMETRIC 1
+#define SFGS_LOSS_DEPTH 2
+#define SFGS_LOSS_L1_STREAM 4
+#define SFGS_LOSS_INVALID_ZERO 0
+#define SFGS_LOSS_INVALID_DROP 1
+#define SFGS_LOSS_INVALID_KEEP 2
+typedef struct SfgsLossArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsLossArgs) */
+  int32_t C, H, W;
+  const float* image;
+  const float* gt_image;
+  const float* depth;
+  const float* gt_depth;
+  const float* mask;
+  int64_t mask_elems;            /* 0, 1 or H * W */
+  float lambda_dssim, lambda_depth;
+  int32_t invalid_mode;          /* SFGS_LOSS_INVALID_*  */
+  int32_t terms;                 /* SFGS_LOSS_* bits     */
+  int32_t with_grad;             /* forward keeps the three SSIM derivative maps in the scratch */
+  int32_t reserved;
+} SfgsLossArgs;
+size_t sfgs_loss_scratch_bytes(const SfgsLossArgs* args);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_loss_forward(const SfgsLossArgs* args, float* out5, void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_loss_backward(const SfgsLossArgs* args, const void* scratch, const float* grad_out5, float* g_image,
+                       float* g_depth, float* g_gt_depth, void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -69,6 +69,18 @@ class SfgsDensifyTensor(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SfgsLossArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("image", C.c_void_p), ("gt_image", C.c_void_p), ("depth", C.c_void_p), ("gt_depth", C.c_void_p),
+                ("mask", C.c_void_p), ("mask_elems", C.c_int64), ("lambda_dssim", C.c_float),
+                ("lambda_depth", C.c_float), ("invalid_mode", C.c_int32), ("terms", C.c_int32),
+                ("with_grad", C.c_int32), ("reserved", C.c_int32)]
+
+
+LOSS_PHOTOMETRIC, LOSS_DEPTH, LOSS_L1_STREAM = 1, 2, 4
+LOSS_INVALID_ZERO, LOSS_INVALID_DROP, LOSS_INVALID_KEEP = 0, 1, 2
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -113,6 +125,9 @@ SYMBOLS = {
     "sfgs_ssim_scratch_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     "sfgs_ssim_forward": (C.c_int, [_V, _V, _I32, _I32, _I32, _I32, _V, _V, _V, _SZ, _I32, _V]),
     "sfgs_ssim_backward": (C.c_int, [_V, _V, _I32, _I32, _I32, _I32, _V, _V, _V, _V]),
+    "sfgs_loss_scratch_bytes": (_SZ, [C.POINTER(SfgsLossArgs)]),
+    "sfgs_loss_forward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _SZ, _V]),
+    "sfgs_loss_backward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _V, _V, _V, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),

@@ -1,0 +1,210 @@
+"""sfgs.loss -- the training loss between render() and loss.backward() (reference train.py:205-234, and :760-799 in the
+IDU episode) on HIP kernels: masked L1 + D-SSIM + Pearson depth term in THREE launches forward and TWO backward
+(csrc/loss.hip through libsfgs.so), with no host read of a device value.
+
+    loss, Ll1, ssim, depth_loss = training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_depth)
+
+replaces (for people who edit their copy of train.py) the four `mask *` products, l1_loss, fused_ssim, the NaN / Inf scrub
+of the depth pair and pearson_corrcoef; all four scalars are differentiable, so a caller can still add terms of its own.
+photometric() and depth_pearson() are the two halves. l1_loss() and pearson_corrcoef() are drop-ins for
+utils.loss_utils.l1_loss and torchmetrics.functional.regression.pearson_corrcoef built on the same kernels;
+install(train_module) rebinds exactly those two names in the module that holds the training loop (and nothing else: no lazy
+tensors, no tensor subclass, no patching of torch or of a class), uninstall(train_module) restores them.
+
+There is no torch fallback: without the HIP library every operator raises."""
+import torch
+
+from . import _lib as L
+
+__all__ = ["training_loss", "photometric", "depth_pearson", "l1_loss", "pearson_corrcoef", "install", "uninstall"]
+
+_INVALID = {"zero": L.LOSS_INVALID_ZERO, "drop": L.LOSS_INVALID_DROP}
+OUT_LOSS, OUT_L1, OUT_SSIM, OUT_DEPTH, OUT_R = range(5)
+
+
+def _check_tensor(name, t, shape_text, ok_shape):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if not ok_shape(t):
+        raise ValueError(f"{name} must be {shape_text}, got {tuple(t.shape)}")
+
+
+def _check_gpu(**tensors):
+    """After every dtype / shape check (those need no device), and still before the library is loaded."""
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must be a GPU tensor")
+
+
+def _check_mask(mask, H, W):
+    if mask is None:
+        return
+    _check_tensor("mask", mask, f"None, (1,1,1) or [1,{H},{W}]",
+                  lambda t: tuple(t.shape) in ((1, 1, 1), (1, H, W)))
+
+
+def _check_invalid(invalid):
+    if invalid not in _INVALID:
+        raise ValueError(f"invalid must be 'zero' or 'drop', got {invalid!r}")
+    return _INVALID[invalid]
+
+
+def _check_images(image, gt_image):
+    _check_tensor("image", image, "[C,H,W]", lambda t: t.dim() == 3 and t.numel() > 0)
+    _check_tensor("gt_image", gt_image, f"{tuple(image.shape)} like image", lambda t: t.shape == image.shape)
+    return tuple(int(v) for v in image.shape)
+
+
+def _check_depths(depth, gt_depth, H=None, W=None):
+    want = "[1,H,W]" if H is None else f"[1,{H},{W}]"
+    _check_tensor("depth", depth, want, lambda t: t.dim() == 3 and t.shape[0] == 1 and t.numel() > 0 and
+                  (H is None or tuple(t.shape[1:]) == (H, W)))
+    _check_tensor("gt_depth", gt_depth, f"{tuple(depth.shape)} like depth", lambda t: t.shape == depth.shape)
+    return int(depth.shape[1]), int(depth.shape[2])
+
+
+class _Loss(torch.autograd.Function):
+    """out5 = (loss, Ll1, ssim, depth_loss, r) from one library call; the backward is one library call too. `first` /
+    `second` are the streaming pair in the reference's argument order (gt_depth, depth)."""
+
+    @staticmethod
+    def forward(ctx, image, gt_image, first, second, mask, shape, lambda_dssim, lambda_depth, invalid, terms):
+        lib = L.load()
+        Cc, H, W = shape
+        ref = image if image is not None else second
+        dev = ref.device
+        with_grad = bool(image is not None and ctx.needs_input_grad[0])
+        args = L.SfgsLossArgs(L.C.sizeof(L.SfgsLossArgs), Cc, H, W,
+                              None if image is None else image.data_ptr(), None if gt_image is None else gt_image.data_ptr(),
+                              None if second is None else second.data_ptr(), None if first is None else first.data_ptr(),
+                              None if mask is None else mask.data_ptr(), 0 if mask is None else mask.numel(),
+                              float(lambda_dssim), float(lambda_depth), int(invalid), int(terms), int(with_grad), 0)
+        with torch.cuda.device(dev):
+            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            nbytes = lib.sfgs_loss_scratch_bytes(L.C.byref(args))
+            if nbytes == 0:
+                raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(5, dtype=torch.float32, device=dev)
+            L.check(lib.sfgs_loss_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), nbytes, stream))
+        ctx.args = args
+        ctx.save_for_backward(scratch, image, gt_image, first, second, mask)   # the pointers in `args` stay valid
+        ctx.want = (with_grad, bool(second is not None and ctx.needs_input_grad[3]),
+                    bool(first is not None and ctx.needs_input_grad[2]))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = L.load()
+        scratch, image, _, first, second, _ = ctx.saved_tensors
+        want_image, want_second, want_first = ctx.want
+        dev = scratch.device
+        with torch.cuda.device(dev):
+            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            g = g_out.contiguous()
+            g_image = torch.empty_like(image) if want_image else None
+            g_second = torch.empty_like(second) if want_second else None
+            g_first = torch.empty_like(first) if want_first else None
+            L.check(lib.sfgs_loss_backward(L.C.byref(ctx.args), L.ptr(scratch), L.ptr(g), L.ptr(g_image), L.ptr(g_second),
+                                           L.ptr(g_first), stream))
+        return g_image, None, g_first, g_second, None, None, None, None, None, None
+
+
+def _mask_arg(mask):
+    return None if mask is None else mask.contiguous().detach()
+
+
+def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_depth, invalid="zero"):
+    """-> (loss, Ll1, ssim, depth_loss), four differentiable device scalars (train.py:205-234 with invalid="zero",
+    :760-799 with invalid="drop"). image, gt_image: [C,H,W]; depth, gt_depth: [1,H,W] or None (then lambda_depth must be
+    0 and depth_loss is 0); mask: None, (1,1,1) or [1,H,W]. Gradients reach image and depth."""
+    mode = _check_invalid(invalid)
+    Cc, H, W = _check_images(image, gt_image)
+    _check_mask(mask, H, W)
+    terms = L.LOSS_PHOTOMETRIC
+    if depth is None or gt_depth is None:
+        if depth is not None or gt_depth is not None:
+            raise ValueError("depth and gt_depth must both be given or both be None")
+        if lambda_depth != 0:
+            raise ValueError("lambda_depth must be 0 without depth and gt_depth")
+    else:
+        _check_depths(depth, gt_depth, H, W)
+        terms |= L.LOSS_DEPTH
+    _check_gpu(image=image, gt_image=gt_image, depth=depth, gt_depth=gt_depth, mask=mask)
+    if depth is not None:
+        depth, gt_depth = depth.contiguous(), gt_depth.contiguous().detach()
+    out = _Loss.apply(image.contiguous(), gt_image.contiguous().detach(), gt_depth, depth, _mask_arg(mask), (Cc, H, W),
+                      lambda_dssim, lambda_depth, mode, terms)
+    o = out.unbind(0)
+    return o[OUT_LOSS], o[OUT_L1], o[OUT_SSIM], o[OUT_DEPTH]
+
+
+def photometric(image, gt_image, mask=None):
+    """-> (Ll1, ssim) of mask * image against mask * gt_image: l1_loss and fused_ssim in one launch (plus the
+    finalisation). Without a mask, or with one of ones, ssim is bit-identical to fused_ssim(image[None], gt_image[None])."""
+    Cc, H, W = _check_images(image, gt_image)
+    _check_mask(mask, H, W)
+    _check_gpu(image=image, gt_image=gt_image, mask=mask)
+    out = _Loss.apply(image.contiguous(), gt_image.contiguous().detach(), None, None, _mask_arg(mask), (Cc, H, W), 0.0, 0.0,
+                      L.LOSS_INVALID_ZERO, L.LOSS_PHOTOMETRIC)
+    o = out.unbind(0)
+    return o[OUT_L1], o[OUT_SSIM]
+
+
+def depth_pearson(depth, gt_depth, mask=None, invalid="zero"):
+    """-> 1 - pearson_corrcoef(mask * gt_depth, mask * depth) with the NaN / Inf scrub of train.py:229-231 ("zero": a pair
+    with a non-finite member becomes (0, 0)) or :788-790 ("drop": it is left out; n = 0 gives NaN)."""
+    mode = _check_invalid(invalid)
+    H, W = _check_depths(depth, gt_depth)
+    _check_mask(mask, H, W)
+    _check_gpu(depth=depth, gt_depth=gt_depth, mask=mask)
+    out = _Loss.apply(None, None, gt_depth.contiguous().detach(), depth.contiguous(), _mask_arg(mask), (1, H, W), 0.0, 0.0,
+                      mode, L.LOSS_DEPTH)
+    return out[OUT_DEPTH]
+
+
+def l1_loss(network_output, gt):
+    """utils.loss_utils.l1_loss: mean |network_output - gt| (one streaming launch plus the finalisation)."""
+    _check_tensor("network_output", network_output, "a non-empty tensor", lambda t: t.numel() > 0)
+    _check_tensor("gt", gt, f"{tuple(network_output.shape)} like network_output", lambda t: t.shape == network_output.shape)
+    _check_gpu(network_output=network_output, gt=gt)
+    n = network_output.numel()
+    out = _Loss.apply(None, None, network_output.contiguous().view(-1), gt.contiguous().view(-1), None, (1, 1, n), 0.0, 0.0,
+                      L.LOSS_INVALID_KEEP, L.LOSS_L1_STREAM)
+    return out[OUT_L1]
+
+
+def pearson_corrcoef(preds, target):
+    """torchmetrics.functional.regression.pearson_corrcoef for float32 [P] or [P,1] inputs: r clamped to [-1, 1], no
+    scrub (a NaN in the inputs gives NaN). Differentiable w.r.t. both arguments."""
+    ok = lambda t: t.numel() > 0 and (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1))
+    _check_tensor("preds", preds, "[P] or [P,1]", ok)
+    _check_tensor("target", target, f"{tuple(preds.shape)} like preds", lambda t: t.shape == preds.shape)
+    _check_gpu(preds=preds, target=target)
+    n = preds.shape[0]
+    out = _Loss.apply(None, None, preds.contiguous().view(-1), target.contiguous().view(-1), None, (1, 1, n), 0.0, 0.0,
+                      L.LOSS_INVALID_KEEP, L.LOSS_DEPTH)
+    return out[OUT_R]
+
+
+_HOOKED = ("l1_loss", "pearson_corrcoef")
+_saved = {}   # module -> the two originals
+
+
+def install(train_module):
+    """Rebind `l1_loss` and `pearson_corrcoef` in the namespace of the module that holds the training loop (train.py
+    looks both up in its globals when called; depth_loss_func reaches pearson_corrcoef the same way). A second install
+    is a no-op."""
+    if train_module in _saved:
+        return
+    _saved[train_module] = {name: getattr(train_module, name) for name in _HOOKED}
+    train_module.l1_loss = l1_loss
+    train_module.pearson_corrcoef = pearson_corrcoef
+
+
+def uninstall(train_module):
+    """Restore what install() replaced. Without an install: a no-op."""
+    for name, fn in _saved.pop(train_module, {}).items():
+        setattr(train_module, name, fn)

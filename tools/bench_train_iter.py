@@ -7,7 +7,11 @@ is the restatement used by tests/test_gpu_training_loop.py.
 REAL=1 (round 6): the same measurement on the reference's OWN code -- scene.gaussian_model.GaussianModel,
 gaussian_renderer.render(), scene.cameras.Camera, utils.loss_utils.l1_loss, imported from /root/reference or the staged archive
 (tools/stage_reference.py) through tests/ref_real_driver.py -- with the statements of train.py:176-340 (render, masked L1 +
-fused_ssim + Pearson depth loss, backward, max_radii2D / add_densification_stats, optimizer.step): no hook vs every hook."""
+fused_ssim + Pearson depth loss, backward, max_radii2D / add_densification_stats, optimizer.step): no hook vs every hook.
+
+LOSS=train|fused (restated variant only; unset: the line above, as every committed profile has it): `train` spells
+train.py:205-234 in torch -- a [1,H,W] mask, a gt_depth, L1 + fused_ssim, the NaN / Inf scrub and the Pearson depth term --
+and `fused` computes the same loss with sfgs.loss.training_loss (three launches forward, two backward)."""
 import importlib.util
 import json
 import os
@@ -134,7 +138,47 @@ gt = torch.rand(3, H, W, generator=gen).cuda()
 bg = torch.zeros(3, device="cuda")
 hooks = [(prepass, loop.GaussianModel), (densify_stats, loop.GaussianModel), (adam, loop.GaussianModel),
          (compact, loop.GaussianModel), (sh, loop.renderer)]
+LOSS = os.environ.get("LOSS", "")
+if LOSS not in ("", "train", "fused"):
+    sys.exit("LOSS must be train or fused")
+if LOSS:
+    from sfgs.loss import training_loss  # noqa: E402
+    original_mask = (torch.rand(1, H, W, generator=gen) < 0.8).float().cuda()
+    original_depth = (300.0 + 20.0 * torch.randn(1, H, W, generator=gen)).cuda()
+
+
+def pearson_corrcoef(preds, target):   # torchmetrics' formula for one update
+    preds, target = preds.squeeze(), target.squeeze()
+    n = preds.shape[0]
+    mx, my = preds.mean(), target.mean()
+    var_x = ((preds - mx) * (preds - mx)).sum() / (n - 1)
+    var_y = ((target - my) * (target - my)).sum() / (n - 1)
+    corr_xy = ((preds - mx) * (target - my)).sum() / (n - 1)
+    return torch.clamp(corr_xy / (var_x * var_y).sqrt(), -1.0, 1.0)
+
+
+def train_loss(image, depth):
+    """train.py:205-234 (lambda_dssim 0.2, lambda_depth 0.5)"""
+    mask = original_mask
+    gt_image = mask * gt
+    gt_depth = mask * original_depth
+    image = mask * image
+    depth = mask * depth
+    Ll1 = torch.abs(image - gt_image).mean()
+    ssim_value = fused_ssim(image.unsqueeze(0), gt_image.unsqueeze(0))
+    loss = (1.0 - 0.2) * Ll1 + 0.2 * (1.0 - ssim_value)
+    gt_depth = gt_depth.reshape(-1, 1)
+    depth = depth.reshape(-1, 1)
+    nan_inf_mask = torch.isnan(depth) | torch.isinf(depth) | torch.isnan(gt_depth) | torch.isinf(gt_depth)
+    depth[nan_inf_mask] = 0.0
+    gt_depth[nan_inf_mask] = 0.0
+    loss += 0.5 * (1 - pearson_corrcoef(gt_depth, depth)).mean()
+    return loss
+
+
 out = {"N": N, "W": W, "H": H}
+if LOSS:
+    out["loss"] = LOSS
 only = os.environ.get("ONLY", "")          # "fused" / "torch": run one variant (for rocprofv3 kernel statistics)
 for fused in (False, True):
     if only and only != ("fused" if fused else "torch"):
@@ -148,8 +192,13 @@ for fused in (False, True):
     def iteration():
         pkg = loop.render(frame, model, bg)
         image, depth = pkg["render"], pkg["render_depth"]
-        loss = 0.8 * (image - gt).abs().mean() + 0.2 * (1.0 - fused_ssim(image.unsqueeze(0), gt.unsqueeze(0)))
-        loss = loss + 1e-3 * torch.nan_to_num(depth, nan=0.0, posinf=0.0, neginf=0.0).mean()
+        if LOSS == "train":
+            loss = train_loss(image, depth)
+        elif LOSS == "fused":
+            loss = training_loss(image, depth.view(1, H, W), gt, original_depth, original_mask, 0.2, 0.5)[0]
+        else:
+            loss = 0.8 * (image - gt).abs().mean() + 0.2 * (1.0 - fused_ssim(image.unsqueeze(0), gt.unsqueeze(0)))
+            loss = loss + 1e-3 * torch.nan_to_num(depth, nan=0.0, posinf=0.0, neginf=0.0).mean()
         loss.backward()
         with torch.no_grad():
             model.add_densification_stats(pkg["viewspace_points"], pkg["visibility_filter"])
