@@ -13,6 +13,7 @@
  *                      autograd backward of that call              train.py:279,845
  *   sfgs_ssim_*        fused_ssim.fused_ssim(img1, img2)           train.py:42,222,778
  *   sfgs_loss_*        the loss statements: mask products, l1_loss, fused_ssim, scrub, pearson_corrcoef   train.py:205-234,760-799
+ *   sfgs_opacity_entropy_*  the opacity regulariser: get_opacity.clamp + binary_cross_entropy(o, o)     train.py:236-242,834-843
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
  *
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 19
+#define SFGS_ABI_VERSION 20
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -431,6 +432,36 @@ size_t sfgs_loss_scratch_bytes(const SfgsLossArgs* args);   /* 0: bad arguments 
 int sfgs_loss_forward(const SfgsLossArgs* args, float* out5, void* scratch, size_t scratch_bytes, void* stream);
 int sfgs_loss_backward(const SfgsLossArgs* args, const void* scratch, const float* grad_out5, float* g_image,
                        float* g_depth, float* g_gt_depth, void* stream);
+
+/* Opacity-entropy regulariser (ABI 20): the lambda_opacity term of train.py:236-242 (and :834-843 in the IDU episode),
+ *     opacity = gaussians.get_opacity.clamp(1.0e-3, 1.0 - 1.0e-3)
+ *     opacity_loss = torch.nn.functional.binary_cross_entropy(opacity, opacity)
+ * on the RAW opacity x[n] (float32, or float64 when is_f64 != 0), two launches forward and one backward, no host read of a
+ * device value, no N-sized scratch:
+ *     o = sigmoid(x), c = min(max(o, lo), hi), inside = (lo <= o <= hi); lo and hi are rounded to x's dtype first, as
+ *     torch's clamp does with Python scalars
+ *     value = mean over n of h(c),  h(c) = -(c log c + (1 - c) log(1 - c))
+ *     grad_raw[i] = g / n * (log(1 - c) - log c) * inside * o (1 - o)     (the cross entropy's derivative with respect to
+ *     its input is exactly 0 when input and target are the same tensor; this is the one with respect to its target)
+ * evaluated in float64 for both dtypes. A NaN in x gives a NaN value and a NaN in that gradient element only; +-Inf gives a
+ * finite value and a zero gradient. The partial sums are reduced in a fixed order: bit-reproducible run to run.
+ * out_scalar, grad_out_scalar (one element each, device memory) and grad_raw[n] have the dtype of opacity_raw. The forward's
+ * scratch holds its per-block partial sums only; the backward needs none of it, but a with_grad != 0 argument block.
+ * Profiler ids (sfgs_profile_kernel_name): opacity_entropy_fwd / _final / _bwd are 27..29, behind the 27 ids of ABI 18 and
+ * in front of the five loss kernels of ABI 19, which move to 30..34 and stay the last of the list. Resolve ids by name. */
+typedef struct SfgsOpacityEntropyArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsOpacityEntropyArgs) */
+  int64_t n;                     /* > 0 */
+  const void* opacity_raw;       /* device pointer, n elements */
+  int32_t is_f64;                /* 0: float32, otherwise float64 */
+  double lo, hi;                 /* 0 < lo < hi < 1 (after rounding to the dtype) */
+  int32_t with_grad;             /* a backward call will follow */
+} SfgsOpacityEntropyArgs;
+size_t sfgs_opacity_entropy_scratch_bytes(const SfgsOpacityEntropyArgs* args);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_opacity_entropy_forward(const SfgsOpacityEntropyArgs* args, void* out_scalar, void* scratch, size_t scratch_bytes,
+                                 void* stream);
+int sfgs_opacity_entropy_backward(const SfgsOpacityEntropyArgs* args, const void* grad_out_scalar, void* grad_raw,
+                                  void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

@@ -53,6 +53,7 @@ static const char* const kKernelNames[KID_COUNT] = {
     "subpix_bound", "preprocess", "bin_count", "bin_rank", "bin_scatter", "plan_scan", "fine_bin", "sort_tiles_small", "sort_tiles_reg_long",
     "sort_tiles_lds", "composite_fwd", "composite_bwd", "preprocess_bwd", "ssim_fwd", "ssim_mean", "ssim_bwd",
     "knn_dist2", "prepass_fwd", "prepass_bwd", "filter3d", "densify_stats", "adam", "sh_eval_fwd", "sh_eval_bwd", "compact_scan", "compact_gather", "densify",
+    "opacity_entropy_fwd", "opacity_entropy_final", "opacity_entropy_bwd",
     "loss_photo_fwd", "loss_depth_fwd", "loss_final", "loss_photo_bwd", "loss_depth_bwd"};
 
 struct ProfRec { int id; hipEvent_t a, b; };

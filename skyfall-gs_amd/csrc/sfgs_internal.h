@@ -34,6 +34,9 @@ void set_error(const char* fmt, ...);
 enum KernelId {
   KID_SUBPIX = 0, KID_PREPROCESS, KID_BIN_COUNT, KID_BIN_RANK, KID_BIN_SCATTER, KID_PLAN_SCAN, KID_FINE_BIN, KID_SORT_SMALL, KID_SORT_REG_LONG, KID_SORT_LDS,
   KID_COMPOSITE_FWD, KID_COMPOSITE_BWD, KID_PREPROCESS_BWD, KID_SSIM_FWD, KID_SSIM_MEAN, KID_SSIM_BWD, KID_KNN, KID_PREPASS_FWD, KID_PREPASS_BWD, KID_FILTER3D, KID_DENSIFY_STATS, KID_ADAM, KID_SH_EVAL_FWD, KID_SH_EVAL_BWD, KID_COMPACT_SCAN, KID_COMPACT_GATHER, KID_DENSIFY,
+  // ABI 20: ids 0..26 are what they were; the three new ones sit BEFORE the loss kernels, whose names stay the last five
+  // that sfgs_profile_kernel_name() lists (tests/test_loss_host.py pins that). Callers resolve ids by name (_lib.profile_select).
+  KID_OPACITY_ENTROPY_FWD, KID_OPACITY_ENTROPY_FINAL, KID_OPACITY_ENTROPY_BWD,
   KID_LOSS_PHOTO_FWD, KID_LOSS_DEPTH_FWD, KID_LOSS_FINAL, KID_LOSS_PHOTO_BWD, KID_LOSS_DEPTH_BWD,
   KID_COUNT
 };

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -81,6 +81,11 @@ LOSS_PHOTOMETRIC, LOSS_DEPTH, LOSS_L1_STREAM = 1, 2, 4
 LOSS_INVALID_ZERO, LOSS_INVALID_DROP, LOSS_INVALID_KEEP = 0, 1, 2
 
 
+class SfgsOpacityEntropyArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int64), ("opacity_raw", C.c_void_p), ("is_f64", C.c_int32),
+                ("lo", C.c_double), ("hi", C.c_double), ("with_grad", C.c_int32)]
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -128,6 +133,9 @@ SYMBOLS = {
     "sfgs_loss_scratch_bytes": (_SZ, [C.POINTER(SfgsLossArgs)]),
     "sfgs_loss_forward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _SZ, _V]),
     "sfgs_loss_backward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _V, _V, _V, _V]),
+    "sfgs_opacity_entropy_scratch_bytes": (_SZ, [C.POINTER(SfgsOpacityEntropyArgs)]),
+    "sfgs_opacity_entropy_forward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _SZ, _V]),
+    "sfgs_opacity_entropy_backward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),

@@ -11,12 +11,19 @@ utils.loss_utils.l1_loss and torchmetrics.functional.regression.pearson_corrcoef
 install(train_module) rebinds exactly those two names in the module that holds the training loop (and nothing else: no lazy
 tensors, no tensor subclass, no patching of torch or of a class), uninstall(train_module) restores them.
 
+    loss = loss + lambda_opacity * opacity_entropy(gaussians._opacity)
+
+is the opacity regulariser of train.py:236-242 / :834-843 (`get_opacity.clamp(1e-3, 1 - 1e-3)` and
+`binary_cross_entropy(opacity, opacity)`) on the raw opacity: two launches forward, one backward (csrc/opacity_reg.hip). The
+route for an UNCHANGED train.py is sfgs.opacity_reg.install(GaussianModel).
+
 There is no torch fallback: without the HIP library every operator raises."""
 import torch
 
 from . import _lib as L
 
-__all__ = ["training_loss", "photometric", "depth_pearson", "l1_loss", "pearson_corrcoef", "install", "uninstall"]
+__all__ = ["training_loss", "photometric", "depth_pearson", "l1_loss", "pearson_corrcoef", "opacity_entropy", "install",
+           "uninstall"]
 
 _INVALID = {"zero": L.LOSS_INVALID_ZERO, "drop": L.LOSS_INVALID_DROP}
 OUT_LOSS, OUT_L1, OUT_SSIM, OUT_DEPTH, OUT_R = range(5)
@@ -187,6 +194,65 @@ def pearson_corrcoef(preds, target):
     out = _Loss.apply(None, None, preds.contiguous().view(-1), target.contiguous().view(-1), None, (1, 1, n), 0.0, 0.0,
                       L.LOSS_INVALID_KEEP, L.LOSS_DEPTH)
     return out[OUT_R]
+
+
+class _OpacityEntropy(torch.autograd.Function):
+    """mean h(clamp(sigmoid(x), lo, hi)) of the raw opacity x, one library call each way; nothing N-sized is saved but x."""
+
+    @staticmethod
+    def forward(ctx, x, lo, hi):
+        lib = L.load()
+        dev = x.device
+        with_grad = bool(ctx.needs_input_grad[0])
+        args = L.SfgsOpacityEntropyArgs(L.C.sizeof(L.SfgsOpacityEntropyArgs), x.numel(), x.data_ptr(),
+                                        int(x.dtype == torch.float64), float(lo), float(hi), int(with_grad))
+        with torch.cuda.device(dev):
+            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            nbytes = lib.sfgs_opacity_entropy_scratch_bytes(L.C.byref(args))
+            if nbytes == 0:
+                raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            out = torch.empty((), dtype=x.dtype, device=dev)
+            L.check(lib.sfgs_opacity_entropy_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), nbytes, stream))
+        ctx.args = args
+        ctx.save_for_backward(x)   # the pointer in `args` stays valid
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        lib = L.load()
+        x, = ctx.saved_tensors
+        dev = x.device
+        with torch.cuda.device(dev):
+            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            g = g_out.contiguous()
+            grad = torch.empty_like(x)
+            L.check(lib.sfgs_opacity_entropy_backward(L.C.byref(ctx.args), L.ptr(g), L.ptr(grad), stream))
+        return grad, None, None
+
+
+def _check_bounds(lo, hi, dtype):
+    """0 < lo < hi < 1 must hold for the bounds as torch's clamp takes them: rounded to the tensor's dtype."""
+    numbers = all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (lo, hi))
+    if not numbers or not 0.0 < torch.tensor(lo, dtype=dtype).item() < torch.tensor(hi, dtype=dtype).item() < 1.0:
+        raise ValueError(f"lo and hi must be numbers with 0 < lo < hi < 1 in {dtype}, got {lo!r}, {hi!r}")
+
+
+def opacity_entropy(opacity_raw, lo=1e-3, hi=1 - 1e-3):
+    """-> mean over the N Gaussians of binary_cross_entropy(o, o), o = sigmoid(opacity_raw).clamp(lo, hi): the
+    lambda_opacity term of train.py:236-242 / :834-843, a differentiable device scalar of the input's dtype.
+    opacity_raw: [N] or [N,1], float32 or float64 (`_opacity` after the first reset_opacity), on the GPU."""
+    if not isinstance(opacity_raw, torch.Tensor):
+        raise ValueError("opacity_raw must be a tensor")
+    if opacity_raw.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"opacity_raw must be float32 or float64, got {opacity_raw.dtype}")
+    if not (opacity_raw.dim() == 1 or (opacity_raw.dim() == 2 and opacity_raw.shape[1] == 1)) or opacity_raw.numel() == 0:
+        raise ValueError(f"opacity_raw must be a non-empty [N] or [N,1], got {tuple(opacity_raw.shape)}")
+    _check_bounds(lo, hi, opacity_raw.dtype)
+    _check_gpu(opacity_raw=opacity_raw)
+    return _OpacityEntropy.apply(opacity_raw.contiguous().view(-1), lo, hi)
 
 
 _HOOKED = ("l1_loss", "pearson_corrcoef")

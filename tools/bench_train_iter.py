@@ -11,7 +11,11 @@ fused_ssim + Pearson depth loss, backward, max_radii2D / add_densification_stats
 
 LOSS=train|fused (restated variant only; unset: the line above, as every committed profile has it): `train` spells
 train.py:205-234 in torch -- a [1,H,W] mask, a gt_depth, L1 + fused_ssim, the NaN / Inf scrub and the Pearson depth term --
-and `fused` computes the same loss with sfgs.loss.training_loss (three launches forward, two backward)."""
+and `fused` computes the same loss with sfgs.loss.training_loss (three launches forward, two backward).
+
+OPACITY=1 (with LOSS=train|fused): adds the opacity regulariser of train.py:236-242 with lambda_opacity = 10 on the model's
+raw opacity -- the torch spelling (sigmoid, clamp, binary_cross_entropy) in the `train` leg, sfgs.loss.opacity_entropy
+(two launches forward, one backward) in the `fused` leg."""
 import importlib.util
 import json
 import os
@@ -141,8 +145,11 @@ hooks = [(prepass, loop.GaussianModel), (densify_stats, loop.GaussianModel), (ad
 LOSS = os.environ.get("LOSS", "")
 if LOSS not in ("", "train", "fused"):
     sys.exit("LOSS must be train or fused")
+OPACITY = os.environ.get("OPACITY", "") not in ("", "0")
+if OPACITY and not LOSS:
+    sys.exit("OPACITY=1 needs LOSS=train or LOSS=fused")
 if LOSS:
-    from sfgs.loss import training_loss  # noqa: E402
+    from sfgs.loss import opacity_entropy, training_loss  # noqa: E402
     original_mask = (torch.rand(1, H, W, generator=gen) < 0.8).float().cuda()
     original_depth = (300.0 + 20.0 * torch.randn(1, H, W, generator=gen)).cuda()
 
@@ -179,6 +186,7 @@ def train_loss(image, depth):
 out = {"N": N, "W": W, "H": H}
 if LOSS:
     out["loss"] = LOSS
+    out["opacity_term"] = OPACITY
 only = os.environ.get("ONLY", "")          # "fused" / "torch": run one variant (for rocprofv3 kernel statistics)
 for fused in (False, True):
     if only and only != ("fused" if fused else "torch"):
@@ -199,6 +207,12 @@ for fused in (False, True):
         else:
             loss = 0.8 * (image - gt).abs().mean() + 0.2 * (1.0 - fused_ssim(image.unsqueeze(0), gt.unsqueeze(0)))
             loss = loss + 1e-3 * torch.nan_to_num(depth, nan=0.0, posinf=0.0, neginf=0.0).mean()
+        if OPACITY and LOSS == "train":        # train.py:239-242 on get_opacity = sigmoid(_opacity)
+            opacity = torch.sigmoid(model._opacity).clamp(1.0e-3, 1.0 - 1.0e-3)
+            opacity_loss = torch.nn.functional.binary_cross_entropy(opacity, opacity)
+            loss += 10.0 * opacity_loss
+        elif OPACITY:
+            loss = loss + 10.0 * opacity_entropy(model._opacity)
         loss.backward()
         with torch.no_grad():
             model.add_densification_stats(pkg["viewspace_points"], pkg["visibility_filter"])
