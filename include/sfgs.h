@@ -14,6 +14,8 @@
  *   sfgs_ssim_*        fused_ssim.fused_ssim(img1, img2)           train.py:42,222,778
  *   sfgs_loss_*        the loss statements: mask products, l1_loss, fused_ssim, scrub, pearson_corrcoef   train.py:205-234,760-799
  *   sfgs_opacity_entropy_*  the opacity regulariser: get_opacity.clamp + binary_cross_entropy(o, o)     train.py:236-242,834-843
+ *   sfgs_depthvis_*    colorize_depth_torch(depth, mask, normalize) render_video.py:129-170, render_video_from_ply.py:126-167, train.py:1001-1041
+ *   sfgs_frame_quantize  (img * 255 + 0.5).clip(0, 255).astype(uint8)  render_video.py:264
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
  *
@@ -35,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 20
+#define SFGS_ABI_VERSION 21
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -462,6 +464,42 @@ int sfgs_opacity_entropy_forward(const SfgsOpacityEntropyArgs* args, void* out_s
                                  void* stream);
 int sfgs_opacity_entropy_backward(const SfgsOpacityEntropyArgs* args, const void* grad_out_scalar, void* grad_raw,
                                   void* stream);
+
+/* Depth colorisation (ABI 21): colorize_depth_torch of render_video.py:129-170 (the same function in
+ * render_video_from_ply.py:126-167 and train.py:1001-1041) without leaving the device. With F = float32, every operation
+ * rounded to float32, divisions correctly rounded, nothing contracted:
+ *     valid = depth > 0 (and mask != 0)                  NaN fails the test; +inf passes and gives disp 0
+ *     disp  = F(1) / depth on valid pixels, NaN elsewhere
+ *     normalize: lo, hi = the 0.01 and 0.99 quantiles of the valid disparities as numpy's nanquantile ("linear") forms
+ *         them on a float32 array: v = the n valid disparities sorted, vi = F(n - 1) * F(q), i = floor(vi), g = vi - i,
+ *         a = v[i], b = v[min(i + 1, n - 1)], d = b - a, r = a + d * g, and r = b - d * (1 - g) when g >= 0.5; n = 0: NaN
+ *         x = 1 - (disp - lo) / (hi - lo);     otherwise x = 1 - disp
+ *     t = x * 256; index k = 255 when t == 256, 0 when t < 0, 255 when t >= 256, trunc(t) otherwise
+ *     pixel = lut[k] (lut: [256][3] uint8 on the device), (0, 0, 0) when x is NaN
+ * v[i] and v[i + 1] of both quantiles are EXACT order statistics: a three-pass radix select (11 + 11 + 10 bits) over the
+ * disparity's bit pattern -- per-workgroup LDS histograms with integer atomics, flushed with integer global atomics, so
+ * the result does not depend on arrival order -- with a one-workgroup scan after every pass. Launches on `stream`:
+ * one memset of the scratch, three histogram passes, three scans, one colourise pass (normalize = 0: the colourise pass
+ * alone; the scratch may then be NULL). The host reads no device value.
+ * out_kind SFGS_DEPTHVIS_FLOAT_CHW: out is float32 [3][H][W] with k / 255 (a correctly rounded division), the reference's
+ * return value; SFGS_DEPTHVIS_UINT8_HWC: out is uint8 [H][W][3], what a video writer takes. */
+#define SFGS_DEPTHVIS_FLOAT_CHW 0
+#define SFGS_DEPTHVIS_UINT8_HWC 1
+typedef struct SfgsDepthVisArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsDepthVisArgs) */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel (bool / uint8), or NULL */
+  const unsigned char* lut;      /* device, [256][3] uint8 */
+  int32_t normalize;             /* != 0: the two quantiles */
+  int32_t out_kind;              /* SFGS_DEPTHVIS_FLOAT_CHW or SFGS_DEPTHVIS_UINT8_HWC */
+} SfgsDepthVisArgs;
+size_t sfgs_depthvis_scratch_bytes(const SfgsDepthVisArgs* args);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_depthvis_forward(const SfgsDepthVisArgs* args, void* out, void* scratch, size_t scratch_bytes, void* stream);
+/* Frame quantiser: image float32 [3][H][W] -> out uint8 [H][W][3] as render_video.py:264 spells it,
+ * (img * 255 + 0.5).clip(0, 255).astype(uint8), in float32 (two roundings, truncation). NaN gives 0 (numpy leaves the
+ * conversion of NaN undefined). One launch. */
+int sfgs_frame_quantize(const float* image, int32_t H, int32_t W, unsigned char* out, void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -86,6 +86,14 @@ class SfgsOpacityEntropyArgs(C.Structure):
                 ("lo", C.c_double), ("hi", C.c_double), ("with_grad", C.c_int32)]
 
 
+class SfgsDepthVisArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p),
+                ("mask", C.c_void_p), ("lut", C.c_void_p), ("normalize", C.c_int32), ("out_kind", C.c_int32)]
+
+
+DEPTHVIS_FLOAT_CHW, DEPTHVIS_UINT8_HWC = 0, 1
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -136,6 +144,9 @@ SYMBOLS = {
     "sfgs_opacity_entropy_scratch_bytes": (_SZ, [C.POINTER(SfgsOpacityEntropyArgs)]),
     "sfgs_opacity_entropy_forward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _SZ, _V]),
     "sfgs_opacity_entropy_backward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _V]),
+    "sfgs_depthvis_scratch_bytes": (_SZ, [C.POINTER(SfgsDepthVisArgs)]),
+    "sfgs_depthvis_forward": (C.c_int, [C.POINTER(SfgsDepthVisArgs), _V, _V, _SZ, _V]),
+    "sfgs_frame_quantize": (C.c_int, [_V, _I32, _I32, _V, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),
