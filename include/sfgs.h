@@ -16,6 +16,8 @@
  *   sfgs_opacity_entropy_*  the opacity regulariser: get_opacity.clamp + binary_cross_entropy(o, o)     train.py:236-242,834-843
  *   sfgs_depthvis_*    colorize_depth_torch(depth, mask, normalize) render_video.py:129-170, render_video_from_ply.py:126-167, train.py:1001-1041
  *   sfgs_frame_quantize  (img * 255 + 0.5).clip(0, 255).astype(uint8)  render_video.py:264
+ *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
+ *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
  *
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 21
+#define SFGS_ABI_VERSION 22
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -500,6 +502,77 @@ int sfgs_depthvis_forward(const SfgsDepthVisArgs* args, void* out, void* scratch
  * (img * 255 + 0.5).clip(0, 255).astype(uint8), in float32 (two roundings, truncation). NaN gives 0 (numpy leaves the
  * conversion of NaN undefined). One launch. */
 int sfgs_frame_quantize(const float* image, int32_t H, int32_t W, unsigned char* out, void* stream);
+
+/* ---- Geometry evaluation (ABI 22; csrc/geometry.hip): evaluate_gs_geometry.py + dsmr.py without their host stages ----------
+ * Stage 1, depth map -> height grid (DSM). One call per view into the SAME accumulators; the merged point cloud is never
+ * formed. A pixel is used when depth > 0, the depth is finite and the mask (one byte per pixel, or NULL) is non-zero. (The
+ * reference's test is depth > 0 alone, which accepts +inf; its caller scrubs +inf to 0 first.) All arithmetic is float64 in
+ * the reference's order (:173-204), nothing contracted:
+ *     z = depth, x = (col - cx_pix) * z / focal_x, y = (row - cy_pix) * z / focal_y
+ *     w_j = ((x M[0][j] + y M[1][j]) + z M[2][j]) + c[j], then + origin[j] as a rounding step of its own   (east, north, up)
+ *     gx = (int)((east - xoff) / resolution), gy = (int)((yoff_top - north) / resolution)       truncation toward zero
+ * M is R transposed (row-major), c = -(M T) and cx_pix = cx / 2 * W + W / 2 (cy_pix alike) are formed by the caller in
+ * float64. A point whose cell lies outside [0, xsize) x [0, ysize) is dropped before any atomic; (-1, 0) truncates to 0,
+ * as in the reference. *num_points (device, uint64) counts the points that landed.
+ * SFGS_DSM_MAX: acc is uint64 [ysize][xsize], zeroed by the caller; every point takes an atomic max with an order-preserving
+ * integer key of its height (0 = empty). SFGS_DSM_MEAN: acc is int64 [ysize][xsize] of heights in units of 2^-20 m
+ * (round to nearest), count uint32 [ysize][xsize], both zeroed by the caller; a point adds to every cell within `radius`
+ * (0 ... 3) columns and rows of its own that lies inside the grid. Integer atomics only: both modes give the same bits
+ * whatever the arrival order. sfgs_dsm_finalize writes float64 [ysize][xsize]: the maximum / sum / count, NaN where empty. */
+#define SFGS_DSM_MAX 0
+#define SFGS_DSM_MEAN 1
+typedef struct SfgsDsmViewArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsDsmViewArgs) */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel, or NULL */
+  double M[9];                   /* camera-to-world rotation, row-major: world = cam @ M + c */
+  double c[3];                   /* camera centre */
+  double origin[3];              /* added after c (the ENU -> UTM translation); zeros for none */
+  double cx_pix, cy_pix, focal_x, focal_y;
+  double xoff, yoff_top, resolution;
+  int32_t xsize, ysize;          /* > 0, xsize * ysize <= 2^28 */
+  int32_t mode;                  /* SFGS_DSM_MAX or SFGS_DSM_MEAN */
+  int32_t radius;                /* mean mode: 0 ... 3 */
+} SfgsDsmViewArgs;
+int sfgs_dsm_accumulate(const SfgsDsmViewArgs* args, void* acc, uint32_t* count, unsigned long long* num_points, void* stream);
+int sfgs_dsm_finalize(int32_t mode, int32_t xsize, int32_t ysize, const void* acc, const uint32_t* count, double* out,
+                      void* stream);
+/* Stage 2, dsmr.compute_shift(ref, sec) on float64 rasters of their own shapes (valnan checks each by its own shape).
+ * Pyramid: while min(ref_h, ref_w) > 100 both rasters are halved by downsample2x (output ceil(H / 2) x ceil(W / 2); cell
+ * (J, I) = the mean of the finite pixels of the 2 x 2 window whose corner is (min(2J + 1, H - 1), min(2I + 1, W - 1)):
+ * the reference's loop lets the last write win); the start (init_dx, init_dy) is floor-halved per level on the way down,
+ * a level starts at twice the result of the level below, read from device memory. Per level: for every shift of
+ * start +- irange, mean_std over the pixels (i, j) of ref paired with sec(i + dx, j + dy), pairs with both values finite
+ * (NaN and +-inf are skipped): means first, then centred sums, sigma = sqrt(sum / count), xcorr = sum / count, score =
+ * xcorr / (sigma_u sigma_v); scan y outer, x inner, update on strict >. A shift with no finite pair or with
+ * sigma_u sigma_v == 0 -- where the reference divides by zero -- is skipped. shift_out: int32 [2] = (dx, dy);
+ * stats_out: float64 [8] = a, b, mu_u, mu_v, sigma_u, sigma_v, xcorr, score at that shift, a = sigma_u / sigma_v with
+ * `scaling`, else 1, b = mu_u - mu_v a. Every shift skipped: (dx, dy) = the start, b and the statistics NaN.
+ * Sums are per 32 x 32 tile of ref, added in tile order by one workgroup: no float atomics, the same bits every run. */
+typedef struct SfgsDsmrArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsDsmrArgs) */
+  int32_t ref_h, ref_w, sec_h, sec_w;   /* 1 ... 32768 */
+  const double* ref;             /* device, [ref_h][ref_w] float64 */
+  const double* sec;             /* device, [sec_h][sec_w] float64 */
+  int32_t irange;                /* 1 ... 7 */
+  int32_t scaling;
+  int32_t init_dx, init_dy;      /* recursive_ncc's dx, dy arguments (compute_shift passes 0, 0) */
+} SfgsDsmrArgs;
+size_t sfgs_dsmr_scratch_bytes(const SfgsDsmrArgs* args);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_dsmr_register(const SfgsDsmrArgs* args, int32_t* shift_out, double* stats_out, void* scratch, size_t scratch_bytes,
+                       void* stream);
+/* Stage 3. dsmr.apply_shift_ with c = d = 0: out(i, j) = a sec(i + dx, j + dy) + b, NaN outside; shift int32 [2] and
+ * ab float64 [2] on the device. compute_dsm_metrics + register_dsms_simple: pred and gt float64 [H][W], mask one byte per
+ * pixel (non-zero = keep) or NULL, shift / ab both NULL or both set (the shifted prediction is formed on the fly);
+ * valid = not NaN. out: float64 [5] = mae, rmse, valid_pixels, completeness (0 when gt has no valid pixel), mean of
+ * gt - pred over the pixels valid in both (0 when none). No valid pixel: NaN, NaN, 0, 0. Per-workgroup partials added in
+ * a fixed order. */
+int sfgs_dsm_apply_shift(const double* sec, int32_t H, int32_t W, const int32_t* shift, const double* ab, double* out,
+                         void* stream);
+size_t sfgs_dsm_metrics_scratch_bytes(int32_t H, int32_t W);   /* 0: bad arguments */
+int sfgs_dsm_metrics(const double* pred, const double* gt, const unsigned char* mask, int32_t H, int32_t W,
+                     const int32_t* shift, const double* ab, double* out, void* scratch, size_t scratch_bytes, void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -94,6 +94,23 @@ class SfgsDepthVisArgs(C.Structure):
 DEPTHVIS_FLOAT_CHW, DEPTHVIS_UINT8_HWC = 0, 1
 
 
+class SfgsDsmViewArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("mask", C.c_void_p),
+                ("M", C.c_double * 9), ("c", C.c_double * 3), ("origin", C.c_double * 3), ("cx_pix", C.c_double),
+                ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double), ("xoff", C.c_double),
+                ("yoff_top", C.c_double), ("resolution", C.c_double), ("xsize", C.c_int32), ("ysize", C.c_int32),
+                ("mode", C.c_int32), ("radius", C.c_int32)]
+
+
+class SfgsDsmrArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ref_h", C.c_int32), ("ref_w", C.c_int32), ("sec_h", C.c_int32),
+                ("sec_w", C.c_int32), ("ref", C.c_void_p), ("sec", C.c_void_p), ("irange", C.c_int32), ("scaling", C.c_int32),
+                ("init_dx", C.c_int32), ("init_dy", C.c_int32)]
+
+
+DSM_MAX, DSM_MEAN = 0, 1
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -147,6 +164,13 @@ SYMBOLS = {
     "sfgs_depthvis_scratch_bytes": (_SZ, [C.POINTER(SfgsDepthVisArgs)]),
     "sfgs_depthvis_forward": (C.c_int, [C.POINTER(SfgsDepthVisArgs), _V, _V, _SZ, _V]),
     "sfgs_frame_quantize": (C.c_int, [_V, _I32, _I32, _V, _V]),
+    "sfgs_dsm_accumulate": (C.c_int, [C.POINTER(SfgsDsmViewArgs), _V, _V, _V, _V]),
+    "sfgs_dsm_finalize": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V]),
+    "sfgs_dsmr_scratch_bytes": (_SZ, [C.POINTER(SfgsDsmrArgs)]),
+    "sfgs_dsmr_register": (C.c_int, [C.POINTER(SfgsDsmrArgs), _V, _V, _V, _SZ, _V]),
+    "sfgs_dsm_apply_shift": (C.c_int, [_V, _I32, _I32, _V, _V, _V, _V]),
+    "sfgs_dsm_metrics_scratch_bytes": (_SZ, [_I32, _I32]),
+    "sfgs_dsm_metrics": (C.c_int, [_V, _V, _V, _I32, _I32, _V, _V, _V, _V, _SZ, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),
