@@ -13,6 +13,7 @@
  *                      autograd backward of that call              train.py:279,845
  *   sfgs_ssim_*        fused_ssim.fused_ssim(img1, img2)           train.py:42,222,778
  *   sfgs_loss_*        the loss statements: mask products, l1_loss, fused_ssim, scrub, pearson_corrcoef   train.py:205-234,760-799
+ *   sfgs_resample_gt   create_offset_gt(mask * original_image, subpixel_offset): meshgrid + grid_sample   train.py:64-77,207,214-215,770-771
  *   sfgs_opacity_entropy_*  the opacity regulariser: get_opacity.clamp + binary_cross_entropy(o, o)     train.py:236-242,834-843
  *   sfgs_depthvis_*    colorize_depth_torch(depth, mask, normalize) render_video.py:129-170, render_video_from_ply.py:126-167, train.py:1001-1041
  *   sfgs_frame_quantize  (img * 255 + 0.5).clip(0, 255).astype(uint8)  render_video.py:264
@@ -39,7 +40,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 22
+#define SFGS_ABI_VERSION 23
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -410,10 +411,15 @@ int sfgs_ssim_backward(const float* img1, const float* img2, int32_t B, int32_t 
  * arbitrary arrays, through the streaming kernels -- the l1_loss drop-in.
  * out5 / grad_out5: five device floats -- loss, Ll1, ssim, depth_loss, r -- and the gradients arriving at them (terms that
  * were not asked for are written as 0). The backward needs the forward's scratch and a with_grad != 0 forward for g_image;
- * g_image [C,H,W], g_depth, g_gt_depth [H*W] may each be NULL (not wanted). */
+ * g_image [C,H,W], g_depth, g_gt_depth [H*W] may each be NULL (not wanted).
+ * SFGS_LOSS_GT_PREMASKED (ABI 23; with SFGS_LOSS_PHOTOMETRIC): gt_image already carries the mask -- y' = gt_image, in the
+ * forward and the backward photometric kernels; x', a and b keep their mask. For a target that was resampled AFTER the mask
+ * product (sfgs_resample_gt; train.py:207 comes before :215): a masked-out pixel next to kept ones is not zero there. With
+ * the bit clear every value and gradient is what ABI 22 computed, bit for bit. */
 #define SFGS_LOSS_PHOTOMETRIC 1
 #define SFGS_LOSS_DEPTH 2
 #define SFGS_LOSS_L1_STREAM 4
+#define SFGS_LOSS_GT_PREMASKED 8
 #define SFGS_LOSS_INVALID_ZERO 0
 #define SFGS_LOSS_INVALID_DROP 1
 #define SFGS_LOSS_INVALID_KEEP 2
@@ -436,6 +442,30 @@ size_t sfgs_loss_scratch_bytes(const SfgsLossArgs* args);   /* 0: bad arguments 
 int sfgs_loss_forward(const SfgsLossArgs* args, float* out5, void* scratch, size_t scratch_bytes, void* stream);
 int sfgs_loss_backward(const SfgsLossArgs* args, const void* scratch, const float* grad_out5, float* g_image,
                        float* g_depth, float* g_gt_depth, void* stream);
+
+/* Jittered ground truth (ABI 23; csrc/resample.hip): create_offset_gt of train.py:64-77 applied to mask * original_image
+ * (train.py:207, 214-215; :770-771 in the IDU episode) -- the target sampled where the jittered rays of
+ * SfgsFrame.subpixel_offset went -- in ONE launch, with no pixel grid, no intermediate tensor and no host read:
+ *     s = mask * src                                   one rounded float32 product per TAP (the mask is applied first)
+ *     u = clamp(x + ox, 0, W - 1), v = clamp(y + oy, 0, H - 1)      grid_sample: bilinear, padding_mode "border",
+ *     x0 = floor(u), fx = u - x0, x1 = min(x0 + 1, W - 1)  (y alike)  align_corners = True; the neighbour index is clamped,
+ *                                                                    its weight is 0 there: nothing is read out of bounds
+ *     out[c][y][x] = ((s[c][y0][x0] (1 - fx)(1 - fy) + s[c][y0][x1] fx (1 - fy)) + s[c][y1][x0] (1 - fx) fy) + s[c][y1][x1] fx fy
+ * every operation rounded to float32, nothing contracted. x + ox is formed directly (the reference divides by W - 1 and
+ * multiplies back: two more roundings at magnitude W). Non-finite offsets behave as in torch's device grid_sample after its
+ * clip: NaN and -inf give 0, +inf gives W - 1 (H - 1). One thread per output pixel, x fastest; deterministic.
+ * src, out: [C][H][W] float32, 1 <= C <= 4, H >= 2, W >= 2 (the reference divides by W - 1 and H - 1), C * H * W < 2^31.
+ * mask: NULL (mask_elems 0), ONE device float (mask_elems 1) or [H*W] -- SfgsLossArgs.mask's three forms. offset: [H][W][2]
+ * float32, channel 0 = x, channel 1 = y. out must not overlap src. No profiler id (as the depthvis kernels). */
+typedef struct SfgsResampleArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsResampleArgs) */
+  int32_t C, H, W;
+  const float* src;
+  const float* mask;
+  int64_t mask_elems;            /* 0, 1 or H * W */
+  const float* offset;
+} SfgsResampleArgs;
+int sfgs_resample_gt(const SfgsResampleArgs* args, float* out, void* stream);
 
 /* Opacity-entropy regulariser (ABI 20): the lambda_opacity term of train.py:236-242 (and :834-843 in the IDU episode),
  *     opacity = gaussians.get_opacity.clamp(1.0e-3, 1.0 - 1.0e-3)

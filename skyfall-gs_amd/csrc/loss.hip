@@ -8,6 +8,8 @@
 // with 16-byte accesses; the Pearson moments are raw sums kept in FLOAT64 (one-pass f32 moments of depths around 400 +- 20
 // miss r by 6e-5). loss_final reduces every partial in a fixed order (no float atomics: bit-reproducible), writes the
 // scalars and leaves the backward's coefficients in the scratch. Nothing here reads a device value on the host.
+// SFGS_LOSS_GT_PREMASKED: the target was resampled after its mask product (resample.hip) and is used AS GIVEN -- the factor on
+// its way to LDS is 1 instead of the mask (x * 1 = x exactly); with the bit clear the factor is the mask, the same product as ever.
 #include "ssim_tile.h"
 
 namespace sfgs {
@@ -31,7 +33,7 @@ __device__ __forceinline__ float scalar_mask(const float* __restrict__ mask, int
 template <bool PLANE>
 __global__ void __launch_bounds__(256)
 loss_photo_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2, const float* __restrict__ mask,
-                      int mask_mode, int H, int W, int tiles_x, int tiles_y, float* __restrict__ ssim_partials,
+                      int mask_mode, int gt_premasked, int H, int W, int tiles_x, int tiles_y, float* __restrict__ ssim_partials,
                       float* __restrict__ l1_partials, float* __restrict__ dm_dmu1, float* __restrict__ dm_dsig1,
                       float* __restrict__ dm_dsig12) {
   __shared__ float s1[SINY][SPITCH], s2[SINY][SPITCH];
@@ -65,7 +67,7 @@ loss_photo_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ 
       const bool in = hl.xin && yin[r];
       const float m = PLANE ? rm[r] : ms;
       s1[4 * r + wv][lane] = in ? m * r1[r] : 0.f;
-      s2[4 * r + wv][lane] = in ? m * r2[r] : 0.f;
+      s2[4 * r + wv][lane] = in ? (gt_premasked ? 1.0f : m) * r2[r] : 0.f;
     }
   }
   __syncthreads();
@@ -141,12 +143,13 @@ loss_photo_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ 
   if (tid == 0) { ssim_partials[T.index] = bs; l1_partials[T.index] = bl; }
 }
 
-// g_image = mask * (w_ssim * (conv0 + 2 x' conv1 + y' conv2) / count + w_l1 * sign(x' - y') / count), x' = mask * image.
+// g_image = mask * (w_ssim * (conv0 + 2 x' conv1 + y' conv2) / count + w_l1 * sign(x' - y') / count), x' = mask * image,
+// y' = mask * gt_image (gt_premasked: gt_image).
 // gin: the incoming gradients of the five outputs (device memory, OUT_*).
 template <bool PLANE>
 __global__ void __launch_bounds__(256)
 loss_photo_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2, const float* __restrict__ mask,
-                      int mask_mode, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ dm_dmu1,
+                      int mask_mode, int gt_premasked, int H, int W, int tiles_x, int tiles_y, const float* __restrict__ dm_dmu1,
                       const float* __restrict__ dm_dsig1, const float* __restrict__ dm_dsig12,
                       const float* __restrict__ gin, float lambda_dssim, float one_minus_lambda, float inv_count,
                       float* __restrict__ dL_dimg1) {
@@ -224,7 +227,7 @@ loss_photo_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ 
   for (int q = 0; q < SQV; ++q) {
     const int gy = y0 + ly0 + q;
     if (gx < W && gy < H && ly0 + q < STY) {
-      const float x = pm[q] * p1[q], y = pm[q] * p2[q], d = x - y;
+      const float x = pm[q] * p1[q], y = (gt_premasked ? 1.0f : pm[q]) * p2[q], d = x - y;
       const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
       bstore(pm[q] * (scale * (mo[0][q] + 2.f * x * mo[1][q] + y * mo[2][q]) + scale_l1 * sgn), og, vout,
              (uint32_t)((y0 + q) * W + x0) * 4u);
@@ -445,7 +448,7 @@ using namespace sfgs;
 namespace {
 
 struct LossPlan {
-  int C, H, W, tiles_x, tiles_y, mask_mode;
+  int C, H, W, tiles_x, tiles_y, mask_mode, gt_premasked;
   bool photo, depth, l1_stream, with_grad;
   size_t n_photo;         // tiles = partials of the photometric kernels
   long long n_stream;     // elements of the streaming pass
@@ -463,8 +466,11 @@ int loss_plan(const SfgsLossArgs* a, LossPlan* p) {
   SFGS_REQUIRE(a, SFGS_E_ARG, "NULL SfgsLossArgs");
   SFGS_REQUIRE(a->struct_size == sizeof(SfgsLossArgs), SFGS_E_ARG, "SfgsLossArgs.struct_size %u, expected %zu",
                a->struct_size, sizeof(SfgsLossArgs));
-  SFGS_REQUIRE((a->terms & ~(SFGS_LOSS_PHOTOMETRIC | SFGS_LOSS_DEPTH | SFGS_LOSS_L1_STREAM)) == 0 && a->terms != 0,
+  SFGS_REQUIRE((a->terms & ~(SFGS_LOSS_PHOTOMETRIC | SFGS_LOSS_DEPTH | SFGS_LOSS_L1_STREAM | SFGS_LOSS_GT_PREMASKED)) == 0 &&
+                   (a->terms & ~SFGS_LOSS_GT_PREMASKED) != 0,
                SFGS_E_ARG, "SfgsLossArgs.terms %d names no term or an unknown one", a->terms);
+  SFGS_REQUIRE(!(a->terms & SFGS_LOSS_GT_PREMASKED) || (a->terms & SFGS_LOSS_PHOTOMETRIC), SFGS_E_ARG,
+               "SFGS_LOSS_GT_PREMASKED needs SFGS_LOSS_PHOTOMETRIC");
   SFGS_REQUIRE(!((a->terms & SFGS_LOSS_L1_STREAM) && (a->terms != SFGS_LOSS_L1_STREAM)), SFGS_E_ARG,
                "SFGS_LOSS_L1_STREAM stands alone");
   SFGS_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0, SFGS_E_ARG, "bad image shape [%d,%d,%d]", a->C, a->H, a->W);
@@ -477,6 +483,7 @@ int loss_plan(const SfgsLossArgs* a, LossPlan* p) {
   p->C = a->C; p->H = a->H; p->W = a->W;
   p->photo = a->terms & SFGS_LOSS_PHOTOMETRIC; p->depth = a->terms & SFGS_LOSS_DEPTH;
   p->l1_stream = a->terms & SFGS_LOSS_L1_STREAM; p->with_grad = a->with_grad != 0;
+  p->gt_premasked = (a->terms & SFGS_LOSS_GT_PREMASKED) ? 1 : 0;
   p->mask_mode = a->mask_elems == 0 ? MASK_NONE : (a->mask_elems == 1 ? MASK_SCALAR : MASK_PLANE);
   p->tiles_x = (a->W + ST - 1) / ST; p->tiles_y = (a->H + STY - 1) / STY;
   p->n_photo = p->photo ? (size_t)a->C * p->tiles_x * p->tiles_y : 0;
@@ -534,11 +541,11 @@ extern "C" int sfgs_loss_forward(const SfgsLossArgs* args, float* out5, void* sc
     ProfScope ps_(KID_LOSS_PHOTO_FWD, stream);
     if (p.mask_mode == MASK_PLANE)
       hipLaunchKernelGGL(loss_photo_fwd_kernel<true>, dim3((unsigned)p.n_photo), dim3(256), 0, stream, args->image,
-                         args->gt_image, args->mask, p.mask_mode, p.H, p.W, p.tiles_x, p.tiles_y, ssim_partials, l1_partials,
+                         args->gt_image, args->mask, p.mask_mode, p.gt_premasked, p.H, p.W, p.tiles_x, p.tiles_y, ssim_partials, l1_partials,
                          m0, m1, m2);
     else
       hipLaunchKernelGGL(loss_photo_fwd_kernel<false>, dim3((unsigned)p.n_photo), dim3(256), 0, stream, args->image,
-                         args->gt_image, args->mask, p.mask_mode, p.H, p.W, p.tiles_x, p.tiles_y, ssim_partials, l1_partials,
+                         args->gt_image, args->mask, p.mask_mode, p.gt_premasked, p.H, p.W, p.tiles_x, p.tiles_y, ssim_partials, l1_partials,
                          m0, m1, m2);
   }
   if (p.photo) SFGS_POST_LAUNCH("loss_photo_fwd", stream, 0);
@@ -581,11 +588,11 @@ extern "C" int sfgs_loss_backward(const SfgsLossArgs* args, const void* scratch,
     ProfScope ps_(KID_LOSS_PHOTO_BWD, stream);
     if (p.mask_mode == MASK_PLANE)
       hipLaunchKernelGGL(loss_photo_bwd_kernel<true>, dim3((unsigned)p.n_photo), dim3(256), 0, stream, args->image,
-                         args->gt_image, args->mask, p.mask_mode, p.H, p.W, p.tiles_x, p.tiles_y, m0, m1, m2, grad_out5,
+                         args->gt_image, args->mask, p.mask_mode, p.gt_premasked, p.H, p.W, p.tiles_x, p.tiles_y, m0, m1, m2, grad_out5,
                          args->lambda_dssim, one_minus, inv_count, g_image);
     else
       hipLaunchKernelGGL(loss_photo_bwd_kernel<false>, dim3((unsigned)p.n_photo), dim3(256), 0, stream, args->image,
-                         args->gt_image, args->mask, p.mask_mode, p.H, p.W, p.tiles_x, p.tiles_y, m0, m1, m2, grad_out5,
+                         args->gt_image, args->mask, p.mask_mode, p.gt_premasked, p.H, p.W, p.tiles_x, p.tiles_y, m0, m1, m2, grad_out5,
                          args->lambda_dssim, one_minus, inv_count, g_image);
   }
   if (g_image) SFGS_POST_LAUNCH("loss_photo_bwd", stream, 0);

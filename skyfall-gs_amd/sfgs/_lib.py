@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -77,8 +77,13 @@ class SfgsLossArgs(C.Structure):
                 ("with_grad", C.c_int32), ("reserved", C.c_int32)]
 
 
-LOSS_PHOTOMETRIC, LOSS_DEPTH, LOSS_L1_STREAM = 1, 2, 4
+LOSS_PHOTOMETRIC, LOSS_DEPTH, LOSS_L1_STREAM, LOSS_GT_PREMASKED = 1, 2, 4, 8
 LOSS_INVALID_ZERO, LOSS_INVALID_DROP, LOSS_INVALID_KEEP = 0, 1, 2
+
+
+class SfgsResampleArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("src", C.c_void_p),
+                ("mask", C.c_void_p), ("mask_elems", C.c_int64), ("offset", C.c_void_p)]
 
 
 class SfgsOpacityEntropyArgs(C.Structure):
@@ -158,6 +163,7 @@ SYMBOLS = {
     "sfgs_loss_scratch_bytes": (_SZ, [C.POINTER(SfgsLossArgs)]),
     "sfgs_loss_forward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _SZ, _V]),
     "sfgs_loss_backward": (C.c_int, [C.POINTER(SfgsLossArgs), _V, _V, _V, _V, _V, _V]),
+    "sfgs_resample_gt": (C.c_int, [C.POINTER(SfgsResampleArgs), _V, _V]),
     "sfgs_opacity_entropy_scratch_bytes": (_SZ, [C.POINTER(SfgsOpacityEntropyArgs)]),
     "sfgs_opacity_entropy_forward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _SZ, _V]),
     "sfgs_opacity_entropy_backward": (C.c_int, [C.POINTER(SfgsOpacityEntropyArgs), _V, _V, _V]),

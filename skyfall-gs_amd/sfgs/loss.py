@@ -17,10 +17,16 @@ is the opacity regulariser of train.py:236-242 / :834-843 (`get_opacity.clamp(1e
 `binary_cross_entropy(opacity, opacity)`) on the raw opacity: two launches forward, one backward (csrc/opacity_reg.hip). The
 route for an UNCHANGED train.py is sfgs.opacity_reg.install(GaussianModel).
 
+training_loss(..., subpixel_offset=offset) and photometric(..., subpixel_offset=offset) are the jittered mode
+(`--ray_jitter --resample_gt_image`, train.py:214-215 / :770-771): the target becomes
+sfgs.resample.resample_gt(gt_image, offset, mask) -- one more launch forward -- and the photometric kernels take it as
+given instead of multiplying the mask in a second time (a masked-out pixel next to kept ones is not zero after resampling).
+
 There is no torch fallback: without the HIP library every operator raises."""
 import torch
 
 from . import _lib as L
+from . import resample as _resample
 
 __all__ = ["training_loss", "photometric", "depth_pearson", "l1_loss", "pearson_corrcoef", "opacity_entropy", "install",
            "uninstall"]
@@ -29,13 +35,7 @@ _INVALID = {"zero": L.LOSS_INVALID_ZERO, "drop": L.LOSS_INVALID_DROP}
 OUT_LOSS, OUT_L1, OUT_SSIM, OUT_DEPTH, OUT_R = range(5)
 
 
-def _check_tensor(name, t, shape_text, ok_shape):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    if not ok_shape(t):
-        raise ValueError(f"{name} must be {shape_text}, got {tuple(t.shape)}")
+_check_tensor = _resample.check_tensor
 
 
 def _check_gpu(**tensors):
@@ -123,13 +123,22 @@ def _mask_arg(mask):
     return None if mask is None else mask.contiguous().detach()
 
 
-def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_depth, invalid="zero"):
+def _jittered_target(gt_image, subpixel_offset, mask, shape):
+    """The checked, contiguous target resampled at the jittered rays (mask applied to the taps): one launch."""
+    return _resample._run(gt_image, subpixel_offset.detach().contiguous(), mask, shape)
+
+
+def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_depth, invalid="zero", subpixel_offset=None):
     """-> (loss, Ll1, ssim, depth_loss), four differentiable device scalars (train.py:205-234 with invalid="zero",
     :760-799 with invalid="drop"). image, gt_image: [C,H,W]; depth, gt_depth: [1,H,W] or None (then lambda_depth must be
-    0 and depth_loss is 0); mask: None, (1,1,1) or [1,H,W]. Gradients reach image and depth."""
+    0 and depth_loss is 0); mask: None, (1,1,1) or [1,H,W]. Gradients reach image and depth.
+    subpixel_offset: None, or the [H,W,2] offsets render() was given (resample_gt_image): mask * image is then compared with
+    resample_gt(gt_image, subpixel_offset, mask); the depth pair keeps its mask."""
     mode = _check_invalid(invalid)
     Cc, H, W = _check_images(image, gt_image)
     _check_mask(mask, H, W)
+    if subpixel_offset is not None:
+        _resample.check_shapes(gt_image, subpixel_offset, None, name="gt_image")
     terms = L.LOSS_PHOTOMETRIC
     if depth is None or gt_depth is None:
         if depth is not None or gt_depth is not None:
@@ -140,22 +149,36 @@ def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_d
         _check_depths(depth, gt_depth, H, W)
         terms |= L.LOSS_DEPTH
     _check_gpu(image=image, gt_image=gt_image, depth=depth, gt_depth=gt_depth, mask=mask)
+    if subpixel_offset is not None:
+        _resample.check_devices(gt_image, subpixel_offset, mask, name="gt_image")
     if depth is not None:
         depth, gt_depth = depth.contiguous(), gt_depth.contiguous().detach()
-    out = _Loss.apply(image.contiguous(), gt_image.contiguous().detach(), gt_depth, depth, _mask_arg(mask), (Cc, H, W),
-                      lambda_dssim, lambda_depth, mode, terms)
+    gt_image, mask = gt_image.contiguous().detach(), _mask_arg(mask)
+    if subpixel_offset is not None:
+        gt_image = _jittered_target(gt_image, subpixel_offset, mask, (Cc, H, W))
+        terms |= L.LOSS_GT_PREMASKED
+    out = _Loss.apply(image.contiguous(), gt_image, gt_depth, depth, mask, (Cc, H, W), lambda_dssim, lambda_depth, mode, terms)
     o = out.unbind(0)
     return o[OUT_LOSS], o[OUT_L1], o[OUT_SSIM], o[OUT_DEPTH]
 
 
-def photometric(image, gt_image, mask=None):
+def photometric(image, gt_image, mask=None, subpixel_offset=None):
     """-> (Ll1, ssim) of mask * image against mask * gt_image: l1_loss and fused_ssim in one launch (plus the
-    finalisation). Without a mask, or with one of ones, ssim is bit-identical to fused_ssim(image[None], gt_image[None])."""
+    finalisation). Without a mask, or with one of ones, ssim is bit-identical to fused_ssim(image[None], gt_image[None]).
+    subpixel_offset: None or [H,W,2] -- the second operand is then resample_gt(gt_image, subpixel_offset, mask), as given."""
     Cc, H, W = _check_images(image, gt_image)
     _check_mask(mask, H, W)
+    if subpixel_offset is not None:
+        _resample.check_shapes(gt_image, subpixel_offset, None, name="gt_image")
     _check_gpu(image=image, gt_image=gt_image, mask=mask)
-    out = _Loss.apply(image.contiguous(), gt_image.contiguous().detach(), None, None, _mask_arg(mask), (Cc, H, W), 0.0, 0.0,
-                      L.LOSS_INVALID_ZERO, L.LOSS_PHOTOMETRIC)
+    if subpixel_offset is not None:
+        _resample.check_devices(gt_image, subpixel_offset, mask, name="gt_image")
+    terms = L.LOSS_PHOTOMETRIC
+    gt_image, mask = gt_image.contiguous().detach(), _mask_arg(mask)
+    if subpixel_offset is not None:
+        gt_image = _jittered_target(gt_image, subpixel_offset, mask, (Cc, H, W))
+        terms |= L.LOSS_GT_PREMASKED
+    out = _Loss.apply(image.contiguous(), gt_image, None, None, mask, (Cc, H, W), 0.0, 0.0, L.LOSS_INVALID_ZERO, terms)
     o = out.unbind(0)
     return o[OUT_L1], o[OUT_SSIM]
 

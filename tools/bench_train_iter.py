@@ -15,7 +15,13 @@ and `fused` computes the same loss with sfgs.loss.training_loss (three launches 
 
 OPACITY=1 (with LOSS=train|fused): adds the opacity regulariser of train.py:236-242 with lambda_opacity = 10 on the model's
 raw opacity -- the torch spelling (sigmoid, clamp, binary_cross_entropy) in the `train` leg, sfgs.loss.opacity_entropy
-(two launches forward, one backward) in the `fused` leg."""
+(two launches forward, one backward) in the `fused` leg.
+
+RESAMPLE=1 (with LOSS=train|fused): the jittered mode, `--ray_jitter --resample_gt_image`. Every iteration draws
+subpixel_offset as train.py:190 does; the `train` leg passes the masked ground truth through the reference's
+create_offset_gt (train.py:64-77: host meshgrid, upload, grid_sample), the `fused` leg gives the offsets to
+sfgs.loss.training_loss(subpixel_offset=...) (one more launch). The restated render() keeps its own zero offsets (the
+rasterizer runs the same path either way); only the target's resampling differs between the legs."""
 import importlib.util
 import json
 import os
@@ -148,6 +154,9 @@ if LOSS not in ("", "train", "fused"):
 OPACITY = os.environ.get("OPACITY", "") not in ("", "0")
 if OPACITY and not LOSS:
     sys.exit("OPACITY=1 needs LOSS=train or LOSS=fused")
+RESAMPLE = os.environ.get("RESAMPLE", "") not in ("", "0")
+if RESAMPLE and not LOSS:
+    sys.exit("RESAMPLE=1 needs LOSS=train or LOSS=fused")
 if LOSS:
     from sfgs.loss import opacity_entropy, training_loss  # noqa: E402
     original_mask = (torch.rand(1, H, W, generator=gen) < 0.8).float().cuda()
@@ -164,13 +173,29 @@ def pearson_corrcoef(preds, target):   # torchmetrics' formula for one update
     return torch.clamp(corr_xy / (var_x * var_y).sqrt(), -1.0, 1.0)
 
 
-def train_loss(image, depth):
+@torch.no_grad()
+def create_offset_gt(image, offset):   # train.py:64-77
+    import numpy as np
+    height, width = image.shape[1:]
+    meshgrid = np.meshgrid(range(width), range(height), indexing='xy')
+    id_coords = np.stack(meshgrid, axis=0).astype(np.float32)
+    id_coords = torch.from_numpy(id_coords).cuda()
+    id_coords = id_coords.permute(1, 2, 0) + offset
+    id_coords[..., 0] /= (width - 1)
+    id_coords[..., 1] /= (height - 1)
+    id_coords = id_coords * 2 - 1
+    return torch.nn.functional.grid_sample(image[None], id_coords[None], align_corners=True, padding_mode="border")[0]
+
+
+def train_loss(image, depth, subpixel_offset=None):
     """train.py:205-234 (lambda_dssim 0.2, lambda_depth 0.5)"""
     mask = original_mask
     gt_image = mask * gt
     gt_depth = mask * original_depth
     image = mask * image
     depth = mask * depth
+    if subpixel_offset is not None:
+        gt_image = create_offset_gt(gt_image, subpixel_offset)
     Ll1 = torch.abs(image - gt_image).mean()
     ssim_value = fused_ssim(image.unsqueeze(0), gt_image.unsqueeze(0))
     loss = (1.0 - 0.2) * Ll1 + 0.2 * (1.0 - ssim_value)
@@ -187,6 +212,8 @@ out = {"N": N, "W": W, "H": H}
 if LOSS:
     out["loss"] = LOSS
     out["opacity_term"] = OPACITY
+    if RESAMPLE:
+        out["resample_gt_image"] = True
 only = os.environ.get("ONLY", "")          # "fused" / "torch": run one variant (for rocprofv3 kernel statistics)
 for fused in (False, True):
     if only and only != ("fused" if fused else "torch"):
@@ -200,10 +227,12 @@ for fused in (False, True):
     def iteration():
         pkg = loop.render(frame, model, bg)
         image, depth = pkg["render"], pkg["render_depth"]
+        offset = (torch.rand((H, W, 2), dtype=torch.float32, device="cuda") - 0.5) if RESAMPLE else None   # train.py:190
         if LOSS == "train":
-            loss = train_loss(image, depth)
+            loss = train_loss(image, depth, offset)
         elif LOSS == "fused":
-            loss = training_loss(image, depth.view(1, H, W), gt, original_depth, original_mask, 0.2, 0.5)[0]
+            loss = training_loss(image, depth.view(1, H, W), gt, original_depth, original_mask, 0.2, 0.5,
+                                 subpixel_offset=offset)[0]
         else:
             loss = 0.8 * (image - gt).abs().mean() + 0.2 * (1.0 - fused_ssim(image.unsqueeze(0), gt.unsqueeze(0)))
             loss = loss + 1e-3 * torch.nan_to_num(depth, nan=0.0, posinf=0.0, neginf=0.0).mean()
