@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 23
+#define SFGS_ABI_VERSION 24
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -236,6 +236,11 @@ typedef struct SfgsRasterCounters {
   int64_t max_bin_items;       /* ALL items of the fullest coarse bin (slab + bin-sorted run): what SFGS_HINT_SHORT_LISTS is
                                   chosen from. Filled by sfgs_raster_counters_decode / sfgs_raster_read_counters; 0 from
                                   sfgs_raster_read_counters_pinned (its 64 bytes end before it) */
+  int64_t sort_wide_tiles;     /* ABI 24: tiles whose list the fused select + sort kernel sorted on the 64-bit (depth, id) key:
+                                  every tile it sorts under "sort_key" = "wide"; otherwise those whose depth range does not fit
+                                  the 32-bit tile-relative key or that hold two entries of equal depth. Produced by the render
+                                  stage like max_tile_list: valid from sfgs_raster_read_counters after the render, 0 elsewhere
+                                  and 0 under the split sort route */
 } SfgsRasterCounters;
 
 int sfgs_abi_version(void);
@@ -243,8 +248,8 @@ const char* sfgs_last_error(void);
 
 /* Process-wide ROUTE options (ABI 16; tests and A/B runs -- never needed for correctness: every route builds bit-identical
  * results, tests/test_gpu_raster.py). They replace the getenv() calls the library used to make on every render: the
- * environment is read ONCE, when the library is loaded (SFGS_SORT, SFGS_PLAN_SCAN, SFGS_BINNING, SFGS_PREFILL, SFGS_KNN, SFGS_TILE_ORDER: same
- * values),
+ * environment is read ONCE, when the library is loaded (SFGS_SORT, SFGS_PLAN_SCAN, SFGS_BINNING, SFGS_PREFILL, SFGS_KNN, SFGS_TILE_ORDER,
+ * SFGS_SORT_KEY: same values),
  * and changed afterwards only through this call. Thread-safe: one atomic word per option; a render running on another
  * thread sees the old or the new value, never a mixture.
  *   key "sort"       "auto" (the frame's launch hints decide) | "fused" | "fused768" | "fused1024" | "split"
@@ -253,6 +258,11 @@ const char* sfgs_last_error(void);
  *   key "prefill"    "auto" (dead-entry prefill decided per frame on the device) | "always" | "never"
  *   key "knn"        "auto" (spatial search above 4 096 points) | "brute" (the exact all-pairs kernel at every size)
  *   key "tile_order" "auto" (SFGS_HINT_TILE_ORDER decides) | "always" | "never": longest-first tile order of the compositing kernels
+ *   key "sort_key"   "auto" (= "narrow" for the kernel's 512-entry form, "wide" for its 768- and 1 024-entry forms) | "narrow": the
+ *                    fused select + sort kernel sorts a tile on one exact 32-bit word per entry
+ *                    (depth bits relative to the tile's nearest entry, above the entry's list position) when the tile's depth
+ *                    range fits it and no two of its entries share a depth, on the 64-bit (depth, id) key otherwise | "wide":
+ *                    the 64-bit key for every tile
  * sfgs_set_option returns SFGS_E_ARG for an unknown key or value; sfgs_get_option returns the current value's name
  * (a string constant) or NULL for an unknown key. */
 int sfgs_set_option(const char* key, const char* value);

@@ -1127,6 +1127,68 @@ __device__ __forceinline__ void wave_bitonic_sort(unsigned long long (&key)[EPL]
   bitonic_sizes<EPL, 2>(key, pay, lane);
 }
 
+// The same network on ONE 32-bit word per element (select_sort_kernel's exact tile-relative key, raster_math.h: sortkey_pack;
+// the word carries the entry's list position, so nothing travels with it): an in-register pair is v_min_u32 + v_max_u32, a
+// cross-lane exchange one shuffle instead of three. Equal words only occur among the padding, where either choice is the same.
+template <int EPL, int SIZE, int STEP>
+__device__ __forceinline__ void bitonic_stage(unsigned (&key)[EPL], int lane) {
+  constexpr int mask = STEP == 0 ? SIZE - 1 : (SIZE >> (STEP + 1));
+  constexpr int rmask = mask & (EPL - 1);
+  constexpr int lmask = mask / EPL;
+  if constexpr (lmask == 0) {
+#pragma unroll
+    for (int r = 0; r < EPL; ++r) {
+      const int q = r ^ rmask;
+      if (q > r) {
+        const unsigned kr = key[r], kq = key[q];
+        key[r] = min(kr, kq); key[q] = max(kr, kq);
+      }
+    }
+  } else {
+    const bool upper = (lane & (lmask & ~(lmask >> 1))) != 0;
+    unsigned nk[EPL];
+#pragma unroll
+    for (int r = 0; r < EPL; ++r) {
+      const unsigned theirs = xor_shuffle<lmask>(key[r ^ rmask]);
+      nk[r] = upper ? max(key[r], theirs) : min(key[r], theirs);
+    }
+#pragma unroll
+    for (int r = 0; r < EPL; ++r) key[r] = nk[r];
+  }
+}
+
+template <int EPL, int SIZE, int STEP>
+__device__ __forceinline__ void bitonic_steps(unsigned (&key)[EPL], int lane) {
+  if constexpr (STEP == 0 || (SIZE >> (STEP + 1)) >= 1) {
+    bitonic_stage<EPL, SIZE, STEP>(key, lane);
+    bitonic_steps<EPL, SIZE, STEP + 1>(key, lane);
+  }
+}
+
+template <int EPL, int SIZE>
+__device__ __forceinline__ void bitonic_sizes(unsigned (&key)[EPL], int lane) {
+  if constexpr (SIZE <= 64 * EPL) {
+    bitonic_steps<EPL, SIZE, 0>(key, lane);
+    bitonic_sizes<EPL, SIZE * 2>(key, lane);
+  }
+}
+
+template <int EPL>
+__device__ __forceinline__ void wave_bitonic_sort(unsigned (&key)[EPL], int lane) {
+  bitonic_sizes<EPL, 2>(key, lane);
+}
+
+// smallest value of the wave, in every lane (uniform): DPP inside a row of 16 lanes, one readlane per row
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
+  v = min(v, xor_shuffle<1>(v));
+  v = min(v, xor_shuffle<2>(v));
+  v = min(v, xor_shuffle<7>(v));    // row_half_mirror: the other quad of the lane's group of 8
+  v = min(v, xor_shuffle<15>(v));   // row_mirror: the other group of 8
+  const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
+  const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+  return min(min(a, b), min(c, d));
+}
+
 // A lane's EPL consecutive list entries (positions lane * EPL ..) as 16-byte (8- / 4-byte) stores instead of EPL dword
 // stores 4 * EPL bytes apart (round 4: one scattered dword store per entry was the expensive way to write a list, cf.
 // profiles/r4_bwd_store3_ab.txt). Every list owns its slots up to the next multiple of 64 (LIST_ALIGN), so a lane whose
@@ -1212,10 +1274,12 @@ sort_tiles_reg_kernel(int T8, const uint2* __restrict__ tile_range, const uint4*
 // IDU cameras (arguments/__init__.py:238-249), which otherwise fell back to fine_bin + two sort kernels).
 // (A wave-level LDS radix sort for the lists beyond 256 entries was built and measured in round 4 -- slower below ~700
 // entries, not kept: profiles/r4_radix_sort_ab_not_kept.txt.)
+// One entry = 12 bytes, as (id, duplicate index) pair + depth bits in arrays of their own: the 32-bit-key sort reads the depths
+// alone and fetches the pair of a sorted entry with one 8-byte read.
 template <int SS_CAP>
 struct alignas(16) SelectSortLds {
-  unsigned long long key[SS_CAP];
-  uint32_t pay[SS_CAP];
+  uint2 idp[SS_CAP];        // (Gaussian id, duplicate index)
+  uint32_t depth[SS_CAP];   // view depth bits
   uint32_t pad_[4];
 };
 
@@ -1227,7 +1291,7 @@ select_sort_kernel(int TX8, int TY8, int CX, int NCB, uint32_t* __restrict__ coa
                    unsigned long long slot_capacity,
                    uint2* __restrict__ tile_range, uint4* __restrict__ items, uint32_t* __restrict__ long_tiles,
                    unsigned long long* __restrict__ hdr, uint32_t* __restrict__ sorted_id,
-                   uint32_t* __restrict__ sorted_dup) {
+                   uint32_t* __restrict__ sorted_dup, int narrow) {
   __shared__ SelectSortLds<SS_CAP> lds_all[COARSE];
   __shared__ unsigned s_cnt[COARSE];
   // workgroup = one row of four tiles of a coarse bin (wave = tile); the four workgroups of a bin are neighbours on one XCD
@@ -1265,8 +1329,8 @@ select_sort_kernel(int TX8, int TY8, int CX, int NCB, uint32_t* __restrict__ coa
         const unsigned pos = atomicAdd(&s_cnt[b - q * COARSE], 1u);
         if (pos < (unsigned)SS_CAP) {
           SelectSortLds<SS_CAP>& dst = lds_all[b - q * COARSE];
-          dst.key[pos] = ((unsigned long long)it[k].y << 32) | it[k].x;
-          dst.pay[pos] = it[k].z + (unsigned)__popc(it[k].w & ((1u << b) - 1u));
+          dst.depth[pos] = it[k].y;
+          dst.idp[pos] = make_uint2(it[k].x, it[k].z + (unsigned)__popc(it[k].w & ((1u << b) - 1u)));
         }
       }
     }
@@ -1294,20 +1358,73 @@ select_sort_kernel(int TX8, int TY8, int CX, int NCB, uint32_t* __restrict__ coa
     const int L = (int)c;
     auto finish = [&](auto epl_tag) {
       constexpr int EPL = decltype(epl_tag)::value;
+      const bool owns = lane * EPL < ((L + LIST_ALIGN - 1) & ~(LIST_ALIGN - 1));   // the tile owns its slots up to the next multiple of 64
+      if (narrow) {
+        // ---- one exact 32-bit word per entry (raster_math.h: sortkey_*): depth bits relative to the tile's nearest entry above
+        // the entry's list position. Taken when the tile's depth range fits the word and no two entries share a depth (then
+        // the word's order IS the (depth, id) order); every other tile is sorted below as before, from the same LDS list.
+        constexpr int PB = SS_CAP <= 512 ? 9 : 10;
+        static_assert(64 * EPL <= (1 << PB), "a list position fits the key's low bits");
+        unsigned key[EPL];
+        unsigned lmin = 0xffffffffu;
+#pragma unroll
+        for (int r = 0; r < EPL; ++r) {
+          const int i = r * 64 + lane;
+          const unsigned d = lds.depth[min(i, SS_CAP - 1)];
+          key[r] = i < L ? d : 0xffffffffu;
+          lmin = min(lmin, key[r]);
+        }
+        const unsigned dmin = wave_min_u32(lmin);
+        bool bad = false;   // (max - min fits) == (every rel fits)
+#pragma unroll
+        for (int r = 0; r < EPL; ++r) {
+          const int i = r * 64 + lane;
+          bad |= i < L && !sortkey_fits(dmin, key[r], PB);
+          key[r] = i < L ? sortkey_pack(key[r], dmin, (unsigned)i, PB) : SORTKEY_PAD;
+        }
+        if (__ballot(bad) == 0ull) {
+          wave_bitonic_sort<EPL>(key, lane);
+          // equal depths: neighbours in the sorted order -- inside the lane, and the next lane's first entry
+          const unsigned next0 = (unsigned)__shfl_down((int)key[0], 1);
+          bool tie = lane < 63 && !sortkey_is_padding(next0) && sortkey_same_depth(key[EPL - 1], next0, PB);
+#pragma unroll
+          for (int r = 0; r + 1 < EPL; ++r)
+            tie |= !sortkey_is_padding(key[r + 1]) && sortkey_same_depth(key[r], key[r + 1], PB);
+          if (__ballot(tie) == 0ull) {
+            const unsigned s = (unsigned)bin_base + (unsigned)__builtin_amdgcn_readfirstlane((int)off);
+            if (lane == 0) tile_range[t] = make_uint2(s, c);
+            if (owns) {
+              unsigned ids[EPL], pay[EPL];
+#pragma unroll
+              for (int r = 0; r < EPL; ++r) {
+                const bool pad = sortkey_is_padding(key[r]);   // the padding's words are what the 64-bit sort leaves there
+                const uint2 e = lds.idp[min(sortkey_pos(key[r], PB), (unsigned)SS_CAP - 1u)];
+                ids[r] = pad ? 0xffffffffu : e.x;
+                pay[r] = pad ? 0u : e.y;
+              }
+              store_list_entries<EPL>(sorted_id + s + lane * EPL, ids);
+              store_list_entries<EPL>(sorted_dup + s + lane * EPL, pay);
+            }
+            return;
+          }
+        }
+      }
+      // ---- 64-bit key (depth bits << 32 | id) + payload
+      if (lane == 0) atomicAdd(&line[8], 1u);   // tiles sorted on the 64-bit key (summed by list_stats)
       unsigned long long key[EPL];
       unsigned pay[EPL];
 #pragma unroll
       for (int r = 0; r < EPL; ++r) {
         const int i = r * 64 + lane;
-        const unsigned long long k = lds.key[min(i, SS_CAP - 1)];
-        const unsigned p = lds.pay[min(i, SS_CAP - 1)];
-        key[r] = i < L ? k : ~0ull;
-        pay[r] = i < L ? p : 0u;
+        const unsigned d = lds.depth[min(i, SS_CAP - 1)];
+        const uint2 e = lds.idp[min(i, SS_CAP - 1)];
+        key[r] = i < L ? (((unsigned long long)d << 32) | e.x) : ~0ull;
+        pay[r] = i < L ? e.y : 0u;
       }
       wave_bitonic_sort<EPL>(key, pay, lane);
       const unsigned s = (unsigned)bin_base + (unsigned)__builtin_amdgcn_readfirstlane((int)off);
       if (lane == 0) tile_range[t] = make_uint2(s, c);
-      if (lane * EPL < ((L + LIST_ALIGN - 1) & ~(LIST_ALIGN - 1))) {   // the tile owns its slots up to the next multiple of 64
+      if (owns) {
         unsigned ids[EPL];
 #pragma unroll
         for (int r = 0; r < EPL; ++r) ids[r] = (unsigned)(key[r] & 0xffffffffull);
@@ -1348,11 +1465,12 @@ select_sort_kernel(int TX8, int TY8, int CX, int NCB, uint32_t* __restrict__ coa
 // frame's plan (SfgsFrame.feedback). Run by the first workgroup of the (always launched) long-list kernel: 256 threads.
 __device__ void list_stats(int NCB, uint32_t* __restrict__ coarse_count, unsigned long long* hdr,
                            unsigned long long* __restrict__ feedback) {
-  __shared__ unsigned ls_part[4], ls_over[4];
-  unsigned m = 0, over = 0;
+  __shared__ unsigned ls_part[4], ls_over[4], ls_wide[4];
+  unsigned m = 0, over = 0, wide = 0;
   for (int i = threadIdx.x; i < NCB; i += 256) {
     m = max(m, coarse_count[(size_t)i * CC_STRIDE + 4]);
     over += coarse_count[(size_t)i * CC_STRIDE + 5];
+    wide += coarse_count[(size_t)i * CC_STRIDE + 8];
     // (a plan is single-use, include/sfgs.h: the bins' slot cursors, their maxima and the header's long-list words are
     // only reset by the next plan's memset)
   }
@@ -1360,12 +1478,14 @@ __device__ void list_stats(int NCB, uint32_t* __restrict__ coarse_count, unsigne
   for (int d = 32; d >= 1; d >>= 1) {
     m = max(m, (unsigned)__shfl_xor((int)m, d));
     over += (unsigned)__shfl_xor((int)over, d);
+    wide += (unsigned)__shfl_xor((int)wide, d);
   }
-  if ((threadIdx.x & 63) == 0) { ls_part[threadIdx.x >> 6] = m; ls_over[threadIdx.x >> 6] = over; }
+  if ((threadIdx.x & 63) == 0) { ls_part[threadIdx.x >> 6] = m; ls_over[threadIdx.x >> 6] = over; ls_wide[threadIdx.x >> 6] = wide; }
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned long long mx = max(max(ls_part[0], ls_part[1]), max(ls_part[2], ls_part[3]));
     hdr[HDR_MAX_LIST] = mx;
+    hdr[HDR_SORT_WIDE] = (unsigned long long)ls_wide[0] + ls_wide[1] + ls_wide[2] + ls_wide[3];
     if (feedback) {
       feedback[FB_VALID] = 1ull;
       feedback[FB_LONG_TILES] = hdr[HDR_LONG_COUNT];
@@ -2256,6 +2376,7 @@ static void unpack_counters(const unsigned long long* h, SfgsRasterCounters* out
   out->overflow = (int64_t)h[HDR_OVERFLOW];
   out->max_coarse_bin = (int64_t)h[HDR_MAX_COARSE];
   out->max_bin_items = (int64_t)h[HDR_MAX_BIN_ITEMS];
+  out->sort_wide_tiles = (int64_t)h[HDR_SORT_WIDE];
   out->num_huge_splats = (int64_t)h[HDR_BIG_COUNT];
   out->num_big_chunks = (int64_t)h[HDR_BIG_CHUNKS];
   out->prev_valid = out->prev_long_tiles = out->prev_max_tile_list = out->prev_prefilled = out->prev_tiles_over_512 = 0;
@@ -2331,22 +2452,27 @@ extern "C" int sfgs_raster_forward_render(const SfgsFrame* frame, int32_t N, con
   const int fused_cap = sort_fused(frame->launch_hints);
   const bool fused = fused_cap != 0;
   if (fused) {
+    // option "sort_key": the short lists' sort on one exact 32-bit word per entry wherever a tile allows it ("narrow"), or on
+    // the 64-bit key everywhere ("wide"); bit-identical lists either way. "auto" = narrow for the 512-entry form only: the
+    // low-elevation regime (lists of 513 .. 652 entries, 768 / 1 024 forms) lost 0.8 % with it, presumably to tiles that pass the
+    // range test, show two equal depths and are sorted twice (profiles/r12_select_sort_narrow_key_ab.txt)
+    const int narrow = option(OPT_SORT_KEY) == SORT_KEY_NARROW || (option(OPT_SORT_KEY) == SORT_KEY_AUTO && fused_cap <= 512);
     { ProfScope ps_(KID_SORT_SMALL, stream);
       if (fused_cap > 768)
         hipLaunchKernelGGL(select_sort_kernel<1024>, dim3((unsigned)NCB * COARSE), dim3(256), 0, stream, TX8, TY8, CX,
                            (int)NCB, tv.coarse_count, bv.csr, bv.slabs, (unsigned)coarse_capacity,
                            (unsigned long long)dup_capacity, tv.tile_range, bv.items, tv.long_tiles, tv.hdr, bv.sorted_id,
-                           bv.sorted_dup);
+                           bv.sorted_dup, narrow);
       else if (fused_cap > 512)   // 36 KB of LDS per workgroup: four workgroups per CU instead of three
         hipLaunchKernelGGL(select_sort_kernel<768>, dim3((unsigned)NCB * COARSE), dim3(256), 0, stream, TX8, TY8, CX,
                            (int)NCB, tv.coarse_count, bv.csr, bv.slabs, (unsigned)coarse_capacity,
                            (unsigned long long)dup_capacity, tv.tile_range, bv.items, tv.long_tiles, tv.hdr, bv.sorted_id,
-                           bv.sorted_dup);
+                           bv.sorted_dup, narrow);
       else
         hipLaunchKernelGGL(select_sort_kernel<512>, dim3((unsigned)NCB * COARSE), dim3(256), 0, stream, TX8, TY8, CX,
                            (int)NCB, tv.coarse_count, bv.csr, bv.slabs, (unsigned)coarse_capacity,
                            (unsigned long long)dup_capacity, tv.tile_range, bv.items, tv.long_tiles, tv.hdr, bv.sorted_id,
-                           bv.sorted_dup); }
+                           bv.sorted_dup, narrow); }
     SFGS_POST_LAUNCH("select_sort", stream, frame->debug);
   } else {
     { ProfScope ps_(KID_FINE_BIN, stream);

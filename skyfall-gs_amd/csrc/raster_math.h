@@ -68,6 +68,30 @@ SFGS_HD int f2i_sat(float v) {
   if (v <= -2147483648.0f) return (-2147483647 - 1);
   return (int)v;
 }
+// ---- the short-list sort's exact 32-bit key (select_sort_kernel, raster_fwd.hip) ------------------------------------------
+// View depths are positive finite floats, so their bit patterns order like their values. Within ONE tile the depths usually span
+// far less than the float range: with rel = depth bits - the tile's smallest depth bits (an integer subtraction, nothing is
+// quantised) and pos = the entry's position in the tile's unsorted list (unique, < 2^pos_bits), the word
+//   key = rel << pos_bits | pos
+// orders exactly as (depth bits, pos): two entries of different depth compare as their depths do. Entries of EQUAL depth compare
+// by pos, not by Gaussian id -- the caller detects them after the sort (sortkey_same_depth on neighbours) and falls back to the
+// 64-bit (depth, id) key. SORTKEY_PAD marks the slots behind the list's end; a tile is sorted by this key only when
+// sortkey_fits(), which leaves every real key strictly below every key of the padding's rel value.
+constexpr uint32_t SORTKEY_PAD = 0xffffffffu;
+// largest depth-bit range (max - min over the tile) the key holds: rel uses the 32 - pos_bits high bits, and their all-ones value
+// belongs to the padding
+SFGS_HD uint32_t sortkey_max_range(int pos_bits) { return (0xffffffffu >> pos_bits) - 1u; }
+SFGS_HD bool sortkey_fits(uint32_t min_depth_bits, uint32_t max_depth_bits, int pos_bits) {
+  return max_depth_bits - min_depth_bits <= sortkey_max_range(pos_bits);
+}
+SFGS_HD uint32_t sortkey_pack(uint32_t depth_bits, uint32_t min_depth_bits, uint32_t pos, int pos_bits) {
+  return ((depth_bits - min_depth_bits) << pos_bits) | pos;
+}
+SFGS_HD uint32_t sortkey_pos(uint32_t key, int pos_bits) { return key & ((1u << pos_bits) - 1u); }
+SFGS_HD uint32_t sortkey_rel(uint32_t key, int pos_bits) { return key >> pos_bits; }
+SFGS_HD bool sortkey_is_padding(uint32_t key) { return key == SORTKEY_PAD; }
+SFGS_HD bool sortkey_same_depth(uint32_t a, uint32_t b, int pos_bits) { return ((a ^ b) >> pos_bits) == 0u; }
+
 SFGS_HD int imin(int a, int b) { return a < b ? a : b; }
 SFGS_HD int imax(int a, int b) { return a > b ? a : b; }
 

@@ -41,8 +41,9 @@ enum KernelId {
   KID_COUNT
 };
 // process-wide route options (include/sfgs.h: sfgs_set_option; api.cpp): one relaxed atomic load per query
-enum { OPT_SORT, OPT_PLAN_SCAN, OPT_BINNING, OPT_PREFILL, OPT_KNN, OPT_TILE_ORDER, OPT_COUNT };
+enum { OPT_SORT, OPT_PLAN_SCAN, OPT_BINNING, OPT_PREFILL, OPT_KNN, OPT_TILE_ORDER, OPT_SORT_KEY, OPT_COUNT };
 enum { SORT_AUTO = 0, SORT_FUSED = 1, SORT_FUSED1024 = 2, SORT_SPLIT = 3, SORT_FUSED768 = 4 };
+enum { SORT_KEY_AUTO = 0, SORT_KEY_WIDE = 1, SORT_KEY_NARROW = 2 };
 enum { PREFILL_AUTO = 0, PREFILL_ALWAYS = 1, PREFILL_NEVER = 2 };
 int option(int which);
 bool prof_enabled();
@@ -132,7 +133,8 @@ enum HeaderSlot {
                          // skips the entries behind a tile's last contributor), else 0
   HDR_CSR_CURSOR = 12,   // two-pass binning: items handed out of BinsView::csr so far (bin_rank_kernel: one atomic per 16 bins)
   HDR_MAX_BIN_ITEMS = 13, // fullest coarse bin counting ALL its items (slab + csr run): what the sort route is chosen from
-  HDR_TILE_ORDER = 14    // bit 0 / 1: TilesView::tile_order holds this frame's longest-first tile order for composite_fwd / _bwd
+  HDR_TILE_ORDER = 14,   // bit 0 / 1: TilesView::tile_order holds this frame's longest-first tile order for composite_fwd / _bwd
+  HDR_SORT_WIDE = 15     // tiles select_sort_kernel sorted on the 64-bit key (all of them under "sort_key" = "wide"); by list_stats
 };
 
 // float4s per compositing record in global memory: 3 = packed 48-byte records; 4 = 64-byte stride (the fourth is never
@@ -196,6 +198,7 @@ struct TilesView {
                             //   word 3 = slots handed out to the bin's tiles so far (select_sort_kernel: one atomic
                             //   per tile), word 4 = the bin's longest tile list (reduced by list_stats), word 5 = the bin's
                             //   tiles with more than 512 entries (select_sort_kernel<1024>; summed by list_stats),
+                            //   word 8 = the bin's tiles that select_sort_kernel sorted on the 64-bit key (summed by list_stats),
                             //   word 6 = first item of the bin's run in BinsView::csr, word 7 = items of that run (two-pass
                             //   binning, bin_rank_kernel; word 0 counts them too: word 0 - word 7 items sit in the bin's slab)
   uint2* tile_range;        // [T8] (first list slot, list length) of every 8x8 tile

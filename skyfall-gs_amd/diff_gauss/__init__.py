@@ -417,6 +417,7 @@ class _Rasterize(torch.autograd.Function):
                     tiles_off = _tiles_offset(lib, N, W, H, cap, ccap, need_bwd)
                     L.check(lib.sfgs_raster_read_counters(scratch.data_ptr() + tiles_off, L.C.byref(full), stream))
                     cnt.max_tile_list = full.max_tile_list
+                    cnt.sort_wide_tiles = full.sort_wide_tiles
                 D, cmax = int(cnt.num_duplicates), int(cnt.max_coarse_bin)
                 if (fwd_hints & HINT_NO_HUGE_SPLATS) and cnt.num_huge_splats:
                     fwd_hints &= ~HINT_NO_HUGE_SPLATS      # this frame HAS splats the skipped walk bins: redo with it
@@ -458,7 +459,7 @@ class _Rasterize(torch.autograd.Function):
             _last_counters = dict(num_duplicates=D, num_duplicates_ref=int(cnt.num_duplicates_ref),
                                   num_visible=int(cnt.num_visible), max_coarse_bin=cmax, max_bin_items=int(cnt.max_bin_items),
                                   num_huge_splats=int(cnt.num_huge_splats), num_big_chunks=int(cnt.num_big_chunks), plan_attempts=attempts,
-                                  max_tile_list=int(cnt.max_tile_list), N=N, W=W, H=H, dup_capacity=cap,
+                                  max_tile_list=int(cnt.max_tile_list), sort_wide_tiles=int(cnt.sort_wide_tiles), N=N, W=W, H=H, dup_capacity=cap,
                                   coarse_capacity=ccap, fwd_hints=int(fwd_hints))   # published by reference assignment (atomic)
         finally:
             if switch:
