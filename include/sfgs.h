@@ -17,6 +17,7 @@
  *   sfgs_opacity_entropy_*  the opacity regulariser: get_opacity.clamp + binary_cross_entropy(o, o)     train.py:236-242,834-843
  *   sfgs_depthvis_*    colorize_depth_torch(depth, mask, normalize) render_video.py:129-170, render_video_from_ply.py:126-167, train.py:1001-1041
  *   sfgs_frame_quantize  (img * 255 + 0.5).clip(0, 255).astype(uint8)  render_video.py:264
+ *   sfgs_metrics_*     the evaluation pass of training_report: clamp, l1_loss, psnr (and ssim)   train.py:1064,1075,1090-1091, utils/image_utils.py:14-19, utils/loss_utils.py:17-18,33-63
  *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
@@ -40,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 24
+#define SFGS_ABI_VERSION 25
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -542,6 +543,41 @@ int sfgs_depthvis_forward(const SfgsDepthVisArgs* args, void* out, void* scratch
  * (img * 255 + 0.5).clip(0, 255).astype(uint8), in float32 (two roundings, truncation). NaN gives 0 (numpy leaves the
  * conversion of NaN undefined). One launch. */
 int sfgs_frame_quantize(const float* image, int32_t H, int32_t W, unsigned char* out, void* stream);
+
+/* Evaluation metrics (ABI 25; csrc/metrics.hip): what training_report computes per view (train.py:1064,1075,1090-1091)
+ *     image = clamp(render, 0, 1); gt_image = clamp(original_image, 0, 1)
+ *     l1_test += l1_loss(image, gt_image).mean().double();  psnr_test += psnr(image, gt_image).mean().double()
+ * with l1_loss = mean |a - b| (utils/loss_utils.py:17-18), psnr = 20 log10(1 / sqrt(mse)) per plane and mse = mean (a - b)^2
+ * per plane (utils/image_utils.py:14-19), and next to them the SSIM of utils/loss_utils.py:33-63 (the fused_ssim kernels'
+ * arithmetic), in TWO launches with no host read of a device value:
+ *     SFGS_METRICS_SSIM set: one workgroup per 32 x 22 tile -- ssim.hip's tile, staging, fma chains and tile order -- writes
+ *         three float partials per tile: the SSIM sum, sum |a - b|, sum (a - b)^2 (a - b and its square rounded to float32)
+ *     clear: a streaming pass (16-byte loads when H * W is a multiple of 4 and both pointers are 16-byte aligned, scalar loads
+ *         otherwise) writes float64 partials of sum |a - b| and sum (a - b)^2 per block; a block never straddles two planes
+ *     one workgroup then sums every partial in float64 in a fixed order (bit-reproducible: no float atomics) and writes
+ *     row8 = [l1, psnr, ssim, mse, psnr_c0, psnr_c1, psnr_c2, psnr_c3]   (float64, device memory):
+ *         l1, mse: means over all P * H * W elements;  psnr_c = 20 log10(1 / sqrt(mse_c)) of plane c, in float64;
+ *         psnr = mean of the P psnr_c;  ssim = mean of the SSIM map (its float32 rounding is fused_ssim's value bit for bit),
+ *         NaN without SFGS_METRICS_SSIM;  psnr_c of planes >= P: NaN.  mse_c = 0 gives +inf; a NaN in plane c gives NaN in
+ *         psnr_c, psnr, l1 and mse -- both as the reference's statements do.
+ * SFGS_METRICS_CLAMP: both operands are clamped to [0, 1] on their way in, NaN staying NaN as in torch.clamp.
+ * SFGS_METRICS_PLANE_MSE: slots 4..7 of the row hold mse_c instead of psnr_c (the utils.image_utils.mse drop-in).
+ * a, b: [P][H][W] float32, 1 <= P <= 4, H * W < 2^30 (a plane is at most 2^32 - 1 bytes); the streaming route uses H * W only.
+ * No profiler ids (as the depthvis kernels). */
+#define SFGS_METRICS_CLAMP 1
+#define SFGS_METRICS_SSIM 2
+#define SFGS_METRICS_PLANE_MSE 4
+typedef struct SfgsMetricsArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsMetricsArgs) */
+  int32_t P;                     /* planes, 1..4 */
+  int32_t H, W;                  /* plane = H x W; the stream route only needs H * W */
+  const float* a;
+  const float* b;
+  int32_t flags;                 /* SFGS_METRICS_* bits */
+  int32_t reserved;
+} SfgsMetricsArgs;
+size_t sfgs_metrics_scratch_bytes(const SfgsMetricsArgs* args);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_metrics_view(const SfgsMetricsArgs* args, double* row8, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- Geometry evaluation (ABI 22; csrc/geometry.hip): evaluate_gs_geometry.py + dsmr.py without their host stages ----------
  * Stage 1, depth map -> height grid (DSM). One call per view into the SAME accumulators; the merged point cloud is never

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -99,6 +99,14 @@ class SfgsDepthVisArgs(C.Structure):
 DEPTHVIS_FLOAT_CHW, DEPTHVIS_UINT8_HWC = 0, 1
 
 
+class SfgsMetricsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("a", C.c_void_p),
+                ("b", C.c_void_p), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+METRICS_CLAMP, METRICS_SSIM, METRICS_PLANE_MSE = 1, 2, 4
+
+
 class SfgsDsmViewArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("mask", C.c_void_p),
                 ("M", C.c_double * 9), ("c", C.c_double * 3), ("origin", C.c_double * 3), ("cx_pix", C.c_double),
@@ -170,6 +178,8 @@ SYMBOLS = {
     "sfgs_depthvis_scratch_bytes": (_SZ, [C.POINTER(SfgsDepthVisArgs)]),
     "sfgs_depthvis_forward": (C.c_int, [C.POINTER(SfgsDepthVisArgs), _V, _V, _SZ, _V]),
     "sfgs_frame_quantize": (C.c_int, [_V, _I32, _I32, _V, _V]),
+    "sfgs_metrics_scratch_bytes": (_SZ, [C.POINTER(SfgsMetricsArgs)]),
+    "sfgs_metrics_view": (C.c_int, [C.POINTER(SfgsMetricsArgs), _V, _V, _SZ, _V]),
     "sfgs_dsm_accumulate": (C.c_int, [C.POINTER(SfgsDsmViewArgs), _V, _V, _V, _V]),
     "sfgs_dsm_finalize": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V]),
     "sfgs_dsmr_scratch_bytes": (_SZ, [C.POINTER(SfgsDsmrArgs)]),
