@@ -3,6 +3,7 @@ fused_ssim(img1, img2, padding="same", train=True) -> scalar mean SSIM, differen
 Semantics == utils/loss_utils.py:23-63. Kernels: skyfall-gs_amd/csrc/ssim.hip via libsfgs.so."""
 import torch
 
+from sfgs import _call
 from sfgs import _lib as L
 
 __all__ = ["fused_ssim"]
@@ -16,12 +17,10 @@ class _FusedSSIM(torch.autograd.Function):
         dev = img1.device
         with_grad = bool(train and ctx.needs_input_grad[0])
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            nbytes = lib.sfgs_ssim_scratch_bytes(B, Cc, H, W, int(with_grad))
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch = _call.scratch(lib.sfgs_ssim_scratch_bytes(B, Cc, H, W, int(with_grad)), dev)
             mean = torch.empty((), dtype=torch.float32, device=dev)
             L.check(lib.sfgs_ssim_forward(L.ptr(img1), L.ptr(img2), B, Cc, H, W, None, L.ptr(mean), L.ptr(scratch),
-                                          scratch.numel(), int(with_grad), stream))
+                                          scratch.numel(), int(with_grad), _call.stream(dev)))
         if with_grad:
             ctx.save_for_backward(img1, img2, scratch)
         return mean
@@ -33,11 +32,10 @@ class _FusedSSIM(torch.autograd.Function):
         B, Cc, H, W = (int(v) for v in img1.shape)
         dev = img1.device
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             g = g_mean.contiguous().float()
             out = torch.empty_like(img1)
             L.check(lib.sfgs_ssim_backward(L.ptr(img1), L.ptr(img2), B, Cc, H, W, L.ptr(scratch), L.ptr(g), L.ptr(out),
-                                           stream))
+                                           _call.stream(dev)))
         return out, None, None
 
 

@@ -260,10 +260,6 @@ def get_option(key):
     return raw.decode()
 
 
-def refresh_options():   # kept for callers of the ABI-16 binding: there is no cache any more
-    pass
-
-
 def box_probe(stream=None):
     """-> (valu_tflops, sclk_mhz_effective) of this box (include/sfgs.h: sfgs_box_probe)."""
     a, b = C.c_double(0.0), C.c_double(0.0)

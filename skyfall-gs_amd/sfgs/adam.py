@@ -13,6 +13,7 @@ and checkpoint capture/restore (`:163-201`) work unchanged. `install(GaussianMod
 after the reference's own `training_setup` built it."""
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["FusedAdam", "install", "uninstall"]
@@ -117,8 +118,7 @@ class FusedAdam(torch.optim.Adam):
         for dev, (recs, _keep, mutated) in per_device.items():
             arr = (L.SfgsAdamTensor * len(recs))(*recs)
             with torch.cuda.device(dev):
-                stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                L.check(L.load().sfgs_adam_step(arr, len(recs), stream))
+                L.check(L.load().sfgs_adam_step(arr, len(recs), _call.stream(dev)))
             # the kernel wrote through raw pointers: tell autograd (and anything keyed on tensor versions, e.g.
             # sfgs.prepass's per-iteration cache) that these tensors changed in place, as torch's own step() does
             for t in mutated:

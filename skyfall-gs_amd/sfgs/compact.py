@@ -9,6 +9,7 @@ the method; `compact_rows` is the underlying utility."""
 import torch
 from torch import nn
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["compact_rows", "prune_points", "install", "uninstall"]
@@ -36,8 +37,8 @@ def compact_rows(keep, tensors):
         srcs.append(t.detach().contiguous())
     lib = L.load()
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        scratch = torch.empty(max(lib.sfgs_compact_scratch_bytes(n), 1), dtype=torch.uint8, device=dev)
+        stream = _call.stream(dev)
+        scratch = _call.scratch(lib.sfgs_compact_scratch_bytes(n), dev)
         kept = L.C.c_int64(0)
         L.check(lib.sfgs_compact_plan(L.ptr(keep8), n, L.ptr(scratch), scratch.numel(), L.C.byref(kept), stream))
         outs = [torch.empty((kept.value,) + tuple(s.shape[1:]), dtype=s.dtype, device=dev) for s in srcs]

@@ -16,16 +16,13 @@ method in."""
 import torch
 from torch import nn
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["quantile_linear", "decide_masks", "densify_and_prune", "zcurve_permutation", "reorder_zcurve", "install",
            "uninstall"]
 
 _SKIP_GROUPS = ("appearance_mlp", "appearance_embeddings")   # shared, not per-Gaussian (scene/gaussian_model.py:607)
-
-
-def _stream(dev):
-    return L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 @torch.no_grad()
@@ -45,9 +42,9 @@ def quantile_linear(values, q):
     rank = (q * (n - 1)).to(torch.float32)          # aten/native/Sorting.cpp: ranks = q * (size - 1)
     out2 = torch.empty(2, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        scratch = torch.empty(lib.sfgs_select_scratch_bytes(), dtype=torch.uint8, device=dev)
+        scratch = _call.scratch(lib.sfgs_select_scratch_bytes(), dev)
         rk = rank.reshape(1).contiguous()
-        L.check(lib.sfgs_select_kth(L.ptr(v), n, L.ptr(rk), L.ptr(out2), L.ptr(scratch), scratch.numel(), _stream(dev)))
+        L.check(lib.sfgs_select_kth(L.ptr(v), n, L.ptr(rk), L.ptr(out2), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
     w = (rank - rank.floor()).to(torch.float32)
     return torch.lerp(out2[0], out2[1], w)
 
@@ -80,11 +77,11 @@ def _decide(model, max_grad, min_opacity, extent, max_screen_size):
     big_thr = float(torch.tensor(0.1 * extent, dtype=torch.float32))                     # :733
     totals = (L.C.c_int64 * 5)()
     with torch.cuda.device(dev):
-        scratch = torch.empty(max(lib.sfgs_densify_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
+        scratch = _call.scratch(lib.sfgs_densify_scratch_bytes(N), dev)
         L.check(lib.sfgs_densify_decide(N, L.ptr(gnorm), L.ptr(gabs), L.ptr(scaling), L.ptr(opacity),
                                         int(opacity.dtype == torch.float64), L.ptr(Q_dev), Q_host, float(max_grad),
                                         float(min_opacity), dense_thr, big_thr, int(bool(max_screen_size)),
-                                        L.ptr(scratch), scratch.numel(), totals, _stream(dev)))
+                                        L.ptr(scratch), scratch.numel(), totals, _call.stream(dev)))
     return scratch, totals, scaling, N, Q_dev
 
 
@@ -99,7 +96,7 @@ def decide_masks(model, max_grad, min_opacity, extent, max_screen_size):
     split = torch.empty(N, dtype=torch.uint8, device=dev)
     keep = torch.empty(N, 3, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.sfgs_densify_masks(N, L.ptr(scratch), L.ptr(clone), L.ptr(split), L.ptr(keep), _stream(dev)))
+        L.check(lib.sfgs_densify_masks(N, L.ptr(scratch), L.ptr(clone), L.ptr(split), L.ptr(keep), _call.stream(dev)))
     return clone.bool(), split.bool(), keep.bool(), Q_dev
 
 
@@ -111,7 +108,7 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, sam
     dev = model._xyz.device
     scratch, totals, scaling, N, _ = _decide(model, max_grad, min_opacity, extent, max_screen_size)
     with torch.cuda.device(dev):
-        stream = _stream(dev)
+        stream = _call.stream(dev)
         n_orig, n_clone, n_child, raw_clone, raw_split = (int(v) for v in totals)
         new_n = n_orig + n_clone + 2 * n_child
         # ---- one gather for every per-Gaussian tensor and its Adam moments ----------------------------------------------

@@ -4,6 +4,7 @@ Reference: scene/gaussian_model.py:744-749 (called every training step below den
 `install(GaussianModel)` swaps the method on the reference's class; semantics and in-place behaviour are identical."""
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["add_densification_stats", "install", "uninstall"]
@@ -28,9 +29,8 @@ def add_densification_stats(model, viewspace_point_tensor, update_filter):
     grad, f = grad.contiguous(), f.contiguous()
     dev = grad.device
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         L.check(L.load().sfgs_densify_stats(N, L.ptr(grad), L.ptr(f), L.ptr(bufs[0]), L.ptr(bufs[1]), L.ptr(bufs[2]),
-                                            L.ptr(bufs[3]), stream))
+                                            L.ptr(bufs[3]), _call.stream(dev)))
     for b in bufs:  # written through raw pointers: bump the autograd version counters like an in-place torch op
         if b is not None:
             torch.autograd.graph.increment_version(b)

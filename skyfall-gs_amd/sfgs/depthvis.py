@@ -19,6 +19,7 @@ There is no torch fallback: without the HIP library every operator raises."""
 import numpy as np
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["colorize_depth", "quantize_frame", "spectral_lut", "spectral_table", "install", "uninstall"]
@@ -78,35 +79,14 @@ def _device_lut(cmap, device):
     return _lut_cache[key]
 
 
-def _check_depth(depth):
-    if not isinstance(depth, torch.Tensor):
-        raise ValueError("depth must be a tensor")
-    if depth.dtype != torch.float32:
-        raise ValueError(f"depth must be float32, got {depth.dtype}")
-    if not ((depth.dim() == 2 or (depth.dim() == 3 and depth.shape[0] == 1)) and depth.numel() > 0):
-        raise ValueError(f"depth must be a non-empty [1,H,W] or [H,W], got {tuple(depth.shape)}")
-    return int(depth.shape[-2]), int(depth.shape[-1])
-
-
-def _check_mask(mask, H, W):
-    if mask is None:
-        return
-    if not isinstance(mask, torch.Tensor):
-        raise ValueError("mask must be a tensor or None")
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"mask must be bool or uint8, got {mask.dtype}")
-    if tuple(mask.shape) not in ((H, W), (1, H, W)):
-        raise ValueError(f"mask must be [{H},{W}] or [1,{H},{W}], got {tuple(mask.shape)}")
-
-
 def colorize_depth(depth, mask=None, normalize=True, cmap="Spectral", out="float_chw", lut=None):
     """The reference's colorize_depth_torch(depth, mask, normalize, cmap) on the device.
     depth: float32 [1,H,W] or [H,W] on the GPU; mask: None, or bool / uint8 of the same H x W (non-zero = use the pixel).
     out="float_chw" -> float32 [3,H,W] with values k / 255 (what the reference returns); out="uint8_hwc" -> uint8 [H,W,3].
     lut: a uint8 [256,3] tensor on depth's device to use instead of the named colormap. cmap other than "Spectral" is
     resolved through matplotlib when it is importable."""
-    H, W = _check_depth(depth)
-    _check_mask(mask, H, W)
+    H, W = _call.check_depth_map(depth)
+    _call.check_pixel_mask(mask, H, W)
     if out not in _OUT:
         raise ValueError(f"out must be 'float_chw' or 'uint8_hwc', got {out!r}")
     if lut is not None:
@@ -114,12 +94,9 @@ def colorize_depth(depth, mask=None, normalize=True, cmap="Spectral", out="float
             raise ValueError("lut must be a uint8 tensor of shape [256,3]")
     elif not isinstance(cmap, str):
         raise ValueError(f"cmap must be a colormap name, got {cmap!r}")
-    if not depth.is_cuda:
-        raise ValueError("depth must be a GPU tensor")
+    _call.check_gpu(depth=depth)
     dev = depth.device
-    for name, t in (("mask", mask), ("lut", lut)):
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} must be on depth's device {dev}, got {t.device}")
+    _call.same_device(dev, "depth's device", mask=mask, lut=lut)
     if lut is None:
         lut = _device_lut(cmap, dev)                      # ValueError for an unknown name
     lib = L.load()
@@ -130,16 +107,13 @@ def colorize_depth(depth, mask=None, normalize=True, cmap="Spectral", out="float
     args = L.SfgsDepthVisArgs(L.C.sizeof(L.SfgsDepthVisArgs), H, W, depth.data_ptr(),
                               None if mask is None else mask.data_ptr(), lut.data_ptr(), int(bool(normalize)), _OUT[out])
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nbytes = lib.sfgs_depthvis_scratch_bytes(L.C.byref(args))
-        if nbytes == 0:
-            raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _call.scratch(lib.sfgs_depthvis_scratch_bytes(L.C.byref(args)), dev, refused_if_zero=True)
         if out == "float_chw":
             result = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         else:
             result = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        L.check(lib.sfgs_depthvis_forward(L.C.byref(args), L.ptr(result), L.ptr(scratch), nbytes, stream))
+        L.check(lib.sfgs_depthvis_forward(L.C.byref(args), L.ptr(result), L.ptr(scratch), scratch.numel(),
+                                          _call.stream(dev)))
     return result
 
 
@@ -147,22 +121,15 @@ def quantize_frame(image):
     """float32 [3,H,W] on the GPU -> uint8 [H,W,3]: `(img * 255 + 0.5).clip(0, 255).astype(np.uint8)` of
     render_video.py:264 on the transposed frame, in float32. NaN gives 0 (numpy leaves the conversion of NaN to an integer
     undefined); -inf gives 0 and +inf 255, as the clip does."""
-    if not isinstance(image, torch.Tensor):
-        raise ValueError("image must be a tensor")
-    if image.dtype != torch.float32:
-        raise ValueError(f"image must be float32, got {image.dtype}")
-    if not (image.dim() == 3 and image.shape[0] == 3 and image.numel() > 0):
-        raise ValueError(f"image must be a non-empty [3,H,W], got {tuple(image.shape)}")
-    if not image.is_cuda:
-        raise ValueError("image must be a GPU tensor")
+    _call.check_tensor("image", image, "a non-empty [3,H,W]", lambda t: t.dim() == 3 and t.shape[0] == 3 and t.numel() > 0)
+    _call.check_gpu(image=image)
     lib = L.load()
     dev = image.device
     image = image.detach().contiguous()
     H, W = int(image.shape[1]), int(image.shape[2])
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         result = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        L.check(lib.sfgs_frame_quantize(L.ptr(image), H, W, L.ptr(result), stream))
+        L.check(lib.sfgs_frame_quantize(L.ptr(image), H, W, L.ptr(result), _call.stream(dev)))
     return result
 
 
@@ -172,21 +139,16 @@ def colorize_depth_torch(depth_tensor, mask=None, normalize=True, cmap='Spectral
     return colorize_depth(depth_tensor[0], None if mask is None else mask[0], normalize=normalize, cmap=cmap)
 
 
-_NAME = "colorize_depth_torch"
-_saved = {}   # module -> its own colorize_depth_torch
+_hook = _call.NameHook(colorize_depth_torch=colorize_depth_torch)
 
 
 def install(module):
     """Rebind `colorize_depth_torch` in the namespace of a module that defines it (train, render_video,
     render_video_from_ply: their loops look the name up in the module's globals when they call it). A second install is a
     no-op; nothing else is patched."""
-    if module in _saved:
-        return
-    _saved[module] = getattr(module, _NAME)
-    setattr(module, _NAME, colorize_depth_torch)
+    _hook.install(module)
 
 
 def uninstall(module):
     """Restore what install() replaced. Without an install: a no-op."""
-    if module in _saved:
-        setattr(module, _NAME, _saved.pop(module))
+    _hook.uninstall(module)

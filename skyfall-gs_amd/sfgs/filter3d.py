@@ -6,6 +6,7 @@ same [N,1] float64 tensor; `install(GaussianModel)` swaps the method on the refe
 import numpy as np
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["compute_3D_filter", "install", "uninstall"]
@@ -39,11 +40,10 @@ def compute_3D_filter(xyz, cameras):
     xyz = xyz.detach().contiguous()
     cams_d = torch.tensor(cams, dtype=torch.float64, device=dev)
     out = torch.empty(N, 1, dtype=torch.float64, device=dev)
-    scratch = torch.empty(max(lib.sfgs_filter3d_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
+    scratch = _call.scratch(lib.sfgs_filter3d_scratch_bytes(N), dev)
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         L.check(lib.sfgs_filter3d(L.ptr(xyz), N, L.ptr(cams_d), len(cams), focal, L.ptr(out), L.ptr(scratch),
-                                  scratch.numel(), stream))
+                                  scratch.numel(), _call.stream(dev)))
     return out
 
 

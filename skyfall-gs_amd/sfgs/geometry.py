@@ -25,6 +25,7 @@ import collections
 import numpy as np
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["DsmGrid", "DsmAccumulator", "DsmShift", "register", "apply_shift", "dsm_metrics", "register_simple", "evaluate_dsm"]
@@ -59,48 +60,12 @@ class DsmGrid(collections.namedtuple("DsmGrid", "xoff yoff_top xsize ysize resol
         return cls(m[0], m[1] + size * res, size, size, res)
 
 
-def _check_depth(depth):
-    if not isinstance(depth, torch.Tensor):
-        raise ValueError("depth must be a tensor")
-    if depth.dtype != torch.float32:
-        raise ValueError(f"depth must be float32, got {depth.dtype}")
-    if not ((depth.dim() == 2 or (depth.dim() == 3 and depth.shape[0] == 1)) and depth.numel() > 0):
-        raise ValueError(f"depth must be a non-empty [1,H,W] or [H,W], got {tuple(depth.shape)}")
-    return int(depth.shape[-2]), int(depth.shape[-1])
-
-
-def _check_mask(mask, H, W, name="mask"):
-    if mask is None:
-        return
-    if not isinstance(mask, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor or None")
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{name} must be bool or uint8, got {mask.dtype}")
-    if tuple(mask.shape) not in ((H, W), (1, H, W)):
-        raise ValueError(f"{name} must be [{H},{W}] or [1,{H},{W}], got {tuple(mask.shape)}")
-
-
 def _check_raster(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor")
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
-    if not (t.dim() == 2 and t.numel() > 0):
-        raise ValueError(f"{name} must be a non-empty [H,W], got {tuple(t.shape)}")
+    _call.check_tensor(name, t, "a non-empty [H,W]", lambda t: t.dim() == 2 and t.numel() > 0,
+                       dtypes=(torch.float32, torch.float64))
     if max(t.shape) > 32768:
         raise ValueError(f"{name}: H and W must not exceed 32768, got {tuple(t.shape)}")
     return int(t.shape[0]), int(t.shape[1])
-
-
-def _need_gpu(t, name):
-    if not t.is_cuda:
-        raise ValueError(f"{name} must be a GPU tensor")
-
-
-def _same_device(dev, **tensors):
-    for name, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} must be on device {dev}, got {t.device}")
 
 
 def _f64(t):
@@ -109,10 +74,6 @@ def _f64(t):
 
 def _u8(mask):
     return None if mask is None else mask.detach().contiguous()
-
-
-def _stream(dev):
-    return L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _vec(x, n, name):
@@ -155,16 +116,16 @@ class DsmAccumulator:
         attributes of the reference's Camera (world-to-camera; cx, cy in normalised units); origin: the three numbers
         enu_to_utm_coordinates adds (UTM easting, northing, altitude of the ENU origin) or None; mask: bool / uint8, non-zero =
         use the pixel."""
-        H, W = _check_depth(depth)
-        _check_mask(mask, H, W)
+        H, W = _call.check_depth_map(depth)
+        _call.check_pixel_mask(mask, H, W)
         R = _vec(R, 9, "R").reshape(3, 3)
         T = _vec(T, 3, "T")
         org = np.zeros(3) if origin is None else _vec(origin, 3, "origin")
         fx, fy, cx, cy = (float(v) for v in (focal_x, focal_y, cx, cy))
         if not (np.isfinite([fx, fy, cx, cy]).all() and fx != 0 and fy != 0):
             raise ValueError(f"focal_x, focal_y must be finite and non-zero, cx, cy finite: got {fx}, {fy}, {cx}, {cy}")
-        _need_gpu(depth, "depth")
-        _same_device(self.device, depth=depth, mask=mask)
+        _call.check_gpu(depth=depth)
+        _call.same_device(self.device, "device", depth=depth, mask=mask)
         M = np.ascontiguousarray(R.T)                     # evaluate_gs_geometry.py:198-201
         c = -M @ T
         lib = L.load()
@@ -176,7 +137,7 @@ class DsmAccumulator:
                                  g.ysize, _MODES[self.mode], self.radius)
         with torch.cuda.device(self.device):
             L.check(lib.sfgs_dsm_accumulate(L.C.byref(args), L.ptr(self._acc), L.ptr(self._count), L.ptr(self._num),
-                                            _stream(self.device)))
+                                            _call.stream(self.device)))
         return self
 
     def add_view(self, depth, camera, origin=None, mask=None):
@@ -191,7 +152,7 @@ class DsmAccumulator:
         out = torch.empty((g.ysize, g.xsize), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             L.check(lib.sfgs_dsm_finalize(_MODES[self.mode], g.xsize, g.ysize, L.ptr(self._acc), L.ptr(self._count), L.ptr(out),
-                                          _stream(self.device)))
+                                          _call.stream(self.device)))
         return out
 
 
@@ -220,34 +181,32 @@ def register(ref, sec, irange=5, scaling=False, init=(0, 0)):
         raise ValueError(f"init must be two integers, got {init!r}") from None
     if max(abs(idx), abs(idy)) > 1 << 20:
         raise ValueError(f"init beyond +-2^20: {init!r}")
-    _need_gpu(ref, "ref")
-    _same_device(ref.device, sec=sec)
+    _call.check_gpu(ref=ref)
+    _call.same_device(ref.device, "device", sec=sec)
     dev = ref.device
     lib = L.load()
     ref, sec = _f64(ref), _f64(sec)
     args = L.SfgsDsmrArgs(L.C.sizeof(L.SfgsDsmrArgs), Hu, Wu, Hv, Wv, ref.data_ptr(), sec.data_ptr(), int(irange),
                           int(bool(scaling)), idx, idy)
     with torch.cuda.device(dev):
-        nbytes = lib.sfgs_dsmr_scratch_bytes(L.C.byref(args))
-        if nbytes == 0:
-            raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _call.scratch(lib.sfgs_dsmr_scratch_bytes(L.C.byref(args)), dev, refused_if_zero=True)
         shift = torch.empty(2, dtype=torch.int32, device=dev)
         stats = torch.empty(8, dtype=torch.float64, device=dev)
-        L.check(lib.sfgs_dsmr_register(L.C.byref(args), L.ptr(shift), L.ptr(stats), L.ptr(scratch), nbytes, _stream(dev)))
+        L.check(lib.sfgs_dsmr_register(L.C.byref(args), L.ptr(shift), L.ptr(stats), L.ptr(scratch), scratch.numel(),
+                                       _call.stream(dev)))
     return DsmShift(shift, stats[:2], stats)
 
 
 def _check_shift(shift, dev):
     if not isinstance(shift, DsmShift):
         raise ValueError("shift must be a DsmShift (the result of register())")
-    _same_device(dev, shift=shift.shift, ab=shift.ab)
+    _call.same_device(dev, "device", shift=shift.shift, ab=shift.ab)
 
 
 def apply_shift(sec, shift):
     """dsmr.apply_shift_ (c = d = 0) -> float64, sec's shape: out(i, j) = a * sec(i + dx, j + dy) + b, NaN outside."""
     H, W = _check_raster(sec, "sec")
-    _need_gpu(sec, "sec")
+    _call.check_gpu(sec=sec)
     _check_shift(shift, sec.device)
     dev = sec.device
     lib = L.load()
@@ -255,7 +214,7 @@ def apply_shift(sec, shift):
     s, ab = shift.shift.contiguous(), shift.ab.contiguous()
     out = torch.empty((H, W), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.sfgs_dsm_apply_shift(L.ptr(sec), H, W, L.ptr(s), L.ptr(ab), L.ptr(out), _stream(dev)))
+        L.check(lib.sfgs_dsm_apply_shift(L.ptr(sec), H, W, L.ptr(s), L.ptr(ab), L.ptr(out), _call.stream(dev)))
     return out
 
 
@@ -264,12 +223,12 @@ def _metrics_raw(pred, gt, shift, mask):
     H, W = _check_raster(pred, "pred")
     if _check_raster(gt, "gt") != (H, W):
         raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape")
-    _check_mask(mask, H, W)
+    _call.check_pixel_mask(mask, H, W)
     if mask is not None and mask.dim() == 3:
         mask = mask[0]
-    _need_gpu(pred, "pred")
+    _call.check_gpu(pred=pred)
     dev = pred.device
-    _same_device(dev, gt=gt, mask=mask)
+    _call.same_device(dev, "device", gt=gt, mask=mask)
     if shift is not None:
         _check_shift(shift, dev)
     lib = L.load()
@@ -277,13 +236,10 @@ def _metrics_raw(pred, gt, shift, mask):
     s = None if shift is None else shift.shift.contiguous()
     ab = None if shift is None else shift.ab.contiguous()
     with torch.cuda.device(dev):
-        nbytes = lib.sfgs_dsm_metrics_scratch_bytes(H, W)
-        if nbytes == 0:
-            raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _call.scratch(lib.sfgs_dsm_metrics_scratch_bytes(H, W), dev, refused_if_zero=True)
         out = torch.empty(5, dtype=torch.float64, device=dev)
         L.check(lib.sfgs_dsm_metrics(L.ptr(pred), L.ptr(gt), L.ptr(mask), H, W, L.ptr(s), L.ptr(ab), L.ptr(out), L.ptr(scratch),
-                                     nbytes, _stream(dev)))
+                                     scratch.numel(), _call.stream(dev)))
     return out
 
 
@@ -312,8 +268,8 @@ def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mod
         raise ValueError(f"{len(view_masks)} view masks for {len(depths)} depth maps")
     if _check_raster(gt_dsm, "gt_dsm") != (grid.ysize, grid.xsize):
         raise ValueError(f"gt_dsm {tuple(gt_dsm.shape)} is not the grid's {(grid.ysize, grid.xsize)}")
-    _check_mask(keep_mask, grid.ysize, grid.xsize, "keep_mask")
-    _need_gpu(gt_dsm, "gt_dsm")
+    _call.check_pixel_mask(keep_mask, grid.ysize, grid.xsize, "keep_mask")
+    _call.check_gpu(gt_dsm=gt_dsm)
     acc = DsmAccumulator(grid, mode=mode, radius=radius, device=gt_dsm.device)
     for k, (depth, cam) in enumerate(zip(depths, cameras)):
         acc.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])

@@ -25,6 +25,7 @@ given instead of multiplying the mask in a second time (a masked-out pixel next 
 There is no torch fallback: without the HIP library every operator raises."""
 import torch
 
+from . import _call
 from . import _lib as L
 from . import resample as _resample
 
@@ -35,21 +36,11 @@ _INVALID = {"zero": L.LOSS_INVALID_ZERO, "drop": L.LOSS_INVALID_DROP}
 OUT_LOSS, OUT_L1, OUT_SSIM, OUT_DEPTH, OUT_R = range(5)
 
 
-_check_tensor = _resample.check_tensor
-
-
-def _check_gpu(**tensors):
-    """After every dtype / shape check (those need no device), and still before the library is loaded."""
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{name} must be a GPU tensor")
-
-
 def _check_mask(mask, H, W):
     if mask is None:
         return
-    _check_tensor("mask", mask, f"None, (1,1,1) or [1,{H},{W}]",
-                  lambda t: tuple(t.shape) in ((1, 1, 1), (1, H, W)))
+    _call.check_tensor("mask", mask, f"None, (1,1,1) or [1,{H},{W}]",
+                       lambda t: tuple(t.shape) in ((1, 1, 1), (1, H, W)))
 
 
 def _check_invalid(invalid):
@@ -59,16 +50,16 @@ def _check_invalid(invalid):
 
 
 def _check_images(image, gt_image):
-    _check_tensor("image", image, "[C,H,W]", lambda t: t.dim() == 3 and t.numel() > 0)
-    _check_tensor("gt_image", gt_image, f"{tuple(image.shape)} like image", lambda t: t.shape == image.shape)
+    _call.check_tensor("image", image, "[C,H,W]", lambda t: t.dim() == 3 and t.numel() > 0)
+    _call.check_tensor("gt_image", gt_image, f"{tuple(image.shape)} like image", lambda t: t.shape == image.shape)
     return tuple(int(v) for v in image.shape)
 
 
 def _check_depths(depth, gt_depth, H=None, W=None):
     want = "[1,H,W]" if H is None else f"[1,{H},{W}]"
-    _check_tensor("depth", depth, want, lambda t: t.dim() == 3 and t.shape[0] == 1 and t.numel() > 0 and
-                  (H is None or tuple(t.shape[1:]) == (H, W)))
-    _check_tensor("gt_depth", gt_depth, f"{tuple(depth.shape)} like depth", lambda t: t.shape == depth.shape)
+    _call.check_tensor("depth", depth, want, lambda t: t.dim() == 3 and t.shape[0] == 1 and t.numel() > 0 and
+                       (H is None or tuple(t.shape[1:]) == (H, W)))
+    _call.check_tensor("gt_depth", gt_depth, f"{tuple(depth.shape)} like depth", lambda t: t.shape == depth.shape)
     return int(depth.shape[1]), int(depth.shape[2])
 
 
@@ -89,13 +80,10 @@ class _Loss(torch.autograd.Function):
                               None if mask is None else mask.data_ptr(), 0 if mask is None else mask.numel(),
                               float(lambda_dssim), float(lambda_depth), int(invalid), int(terms), int(with_grad), 0)
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            nbytes = lib.sfgs_loss_scratch_bytes(L.C.byref(args))
-            if nbytes == 0:
-                raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch = _call.scratch(lib.sfgs_loss_scratch_bytes(L.C.byref(args)), dev, refused_if_zero=True)
             out = torch.empty(5, dtype=torch.float32, device=dev)
-            L.check(lib.sfgs_loss_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), nbytes, stream))
+            L.check(lib.sfgs_loss_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), scratch.numel(),
+                                          _call.stream(dev)))
         ctx.args = args
         ctx.save_for_backward(scratch, image, gt_image, first, second, mask)   # the pointers in `args` stay valid
         ctx.want = (with_grad, bool(second is not None and ctx.needs_input_grad[3]),
@@ -109,13 +97,12 @@ class _Loss(torch.autograd.Function):
         want_image, want_second, want_first = ctx.want
         dev = scratch.device
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             g = g_out.contiguous()
             g_image = torch.empty_like(image) if want_image else None
             g_second = torch.empty_like(second) if want_second else None
             g_first = torch.empty_like(first) if want_first else None
             L.check(lib.sfgs_loss_backward(L.C.byref(ctx.args), L.ptr(scratch), L.ptr(g), L.ptr(g_image), L.ptr(g_second),
-                                           L.ptr(g_first), stream))
+                                           L.ptr(g_first), _call.stream(dev)))
         return g_image, None, g_first, g_second, None, None, None, None, None, None
 
 
@@ -125,7 +112,7 @@ def _mask_arg(mask):
 
 def _jittered_target(gt_image, subpixel_offset, mask, shape):
     """The checked, contiguous target resampled at the jittered rays (mask applied to the taps): one launch."""
-    return _resample._run(gt_image, subpixel_offset.detach().contiguous(), mask, shape)
+    return _resample.run(gt_image, subpixel_offset.detach().contiguous(), mask, shape)
 
 
 def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_depth, invalid="zero", subpixel_offset=None):
@@ -148,7 +135,7 @@ def training_loss(image, depth, gt_image, gt_depth, mask, lambda_dssim, lambda_d
     else:
         _check_depths(depth, gt_depth, H, W)
         terms |= L.LOSS_DEPTH
-    _check_gpu(image=image, gt_image=gt_image, depth=depth, gt_depth=gt_depth, mask=mask)
+    _call.check_gpu(image=image, gt_image=gt_image, depth=depth, gt_depth=gt_depth, mask=mask)
     if subpixel_offset is not None:
         _resample.check_devices(gt_image, subpixel_offset, mask, name="gt_image")
     if depth is not None:
@@ -170,7 +157,7 @@ def photometric(image, gt_image, mask=None, subpixel_offset=None):
     _check_mask(mask, H, W)
     if subpixel_offset is not None:
         _resample.check_shapes(gt_image, subpixel_offset, None, name="gt_image")
-    _check_gpu(image=image, gt_image=gt_image, mask=mask)
+    _call.check_gpu(image=image, gt_image=gt_image, mask=mask)
     if subpixel_offset is not None:
         _resample.check_devices(gt_image, subpixel_offset, mask, name="gt_image")
     terms = L.LOSS_PHOTOMETRIC
@@ -189,7 +176,7 @@ def depth_pearson(depth, gt_depth, mask=None, invalid="zero"):
     mode = _check_invalid(invalid)
     H, W = _check_depths(depth, gt_depth)
     _check_mask(mask, H, W)
-    _check_gpu(depth=depth, gt_depth=gt_depth, mask=mask)
+    _call.check_gpu(depth=depth, gt_depth=gt_depth, mask=mask)
     out = _Loss.apply(None, None, gt_depth.contiguous().detach(), depth.contiguous(), _mask_arg(mask), (1, H, W), 0.0, 0.0,
                       mode, L.LOSS_DEPTH)
     return out[OUT_DEPTH]
@@ -197,9 +184,10 @@ def depth_pearson(depth, gt_depth, mask=None, invalid="zero"):
 
 def l1_loss(network_output, gt):
     """utils.loss_utils.l1_loss: mean |network_output - gt| (one streaming launch plus the finalisation)."""
-    _check_tensor("network_output", network_output, "a non-empty tensor", lambda t: t.numel() > 0)
-    _check_tensor("gt", gt, f"{tuple(network_output.shape)} like network_output", lambda t: t.shape == network_output.shape)
-    _check_gpu(network_output=network_output, gt=gt)
+    _call.check_tensor("network_output", network_output, "a non-empty tensor", lambda t: t.numel() > 0)
+    _call.check_tensor("gt", gt, f"{tuple(network_output.shape)} like network_output",
+                       lambda t: t.shape == network_output.shape)
+    _call.check_gpu(network_output=network_output, gt=gt)
     n = network_output.numel()
     out = _Loss.apply(None, None, network_output.contiguous().view(-1), gt.contiguous().view(-1), None, (1, 1, n), 0.0, 0.0,
                       L.LOSS_INVALID_KEEP, L.LOSS_L1_STREAM)
@@ -210,9 +198,9 @@ def pearson_corrcoef(preds, target):
     """torchmetrics.functional.regression.pearson_corrcoef for float32 [P] or [P,1] inputs: r clamped to [-1, 1], no
     scrub (a NaN in the inputs gives NaN). Differentiable w.r.t. both arguments."""
     ok = lambda t: t.numel() > 0 and (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1))
-    _check_tensor("preds", preds, "[P] or [P,1]", ok)
-    _check_tensor("target", target, f"{tuple(preds.shape)} like preds", lambda t: t.shape == preds.shape)
-    _check_gpu(preds=preds, target=target)
+    _call.check_tensor("preds", preds, "[P] or [P,1]", ok)
+    _call.check_tensor("target", target, f"{tuple(preds.shape)} like preds", lambda t: t.shape == preds.shape)
+    _call.check_gpu(preds=preds, target=target)
     n = preds.shape[0]
     out = _Loss.apply(None, None, preds.contiguous().view(-1), target.contiguous().view(-1), None, (1, 1, n), 0.0, 0.0,
                       L.LOSS_INVALID_KEEP, L.LOSS_DEPTH)
@@ -230,13 +218,10 @@ class _OpacityEntropy(torch.autograd.Function):
         args = L.SfgsOpacityEntropyArgs(L.C.sizeof(L.SfgsOpacityEntropyArgs), x.numel(), x.data_ptr(),
                                         int(x.dtype == torch.float64), float(lo), float(hi), int(with_grad))
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            nbytes = lib.sfgs_opacity_entropy_scratch_bytes(L.C.byref(args))
-            if nbytes == 0:
-                raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            scratch = _call.scratch(lib.sfgs_opacity_entropy_scratch_bytes(L.C.byref(args)), dev, refused_if_zero=True)
             out = torch.empty((), dtype=x.dtype, device=dev)
-            L.check(lib.sfgs_opacity_entropy_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), nbytes, stream))
+            L.check(lib.sfgs_opacity_entropy_forward(L.C.byref(args), L.ptr(out), L.ptr(scratch), scratch.numel(),
+                                                     _call.stream(dev)))
         ctx.args = args
         ctx.save_for_backward(x)   # the pointer in `args` stays valid
         return out
@@ -249,10 +234,9 @@ class _OpacityEntropy(torch.autograd.Function):
         x, = ctx.saved_tensors
         dev = x.device
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             g = g_out.contiguous()
             grad = torch.empty_like(x)
-            L.check(lib.sfgs_opacity_entropy_backward(L.C.byref(ctx.args), L.ptr(g), L.ptr(grad), stream))
+            L.check(lib.sfgs_opacity_entropy_backward(L.C.byref(ctx.args), L.ptr(g), L.ptr(grad), _call.stream(dev)))
         return grad, None, None
 
 
@@ -267,33 +251,24 @@ def opacity_entropy(opacity_raw, lo=1e-3, hi=1 - 1e-3):
     """-> mean over the N Gaussians of binary_cross_entropy(o, o), o = sigmoid(opacity_raw).clamp(lo, hi): the
     lambda_opacity term of train.py:236-242 / :834-843, a differentiable device scalar of the input's dtype.
     opacity_raw: [N] or [N,1], float32 or float64 (`_opacity` after the first reset_opacity), on the GPU."""
-    if not isinstance(opacity_raw, torch.Tensor):
-        raise ValueError("opacity_raw must be a tensor")
-    if opacity_raw.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"opacity_raw must be float32 or float64, got {opacity_raw.dtype}")
-    if not (opacity_raw.dim() == 1 or (opacity_raw.dim() == 2 and opacity_raw.shape[1] == 1)) or opacity_raw.numel() == 0:
-        raise ValueError(f"opacity_raw must be a non-empty [N] or [N,1], got {tuple(opacity_raw.shape)}")
+    _call.check_tensor("opacity_raw", opacity_raw, "a non-empty [N] or [N,1]",
+                       lambda t: (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)) and t.numel() > 0,
+                       dtypes=(torch.float32, torch.float64))
     _check_bounds(lo, hi, opacity_raw.dtype)
-    _check_gpu(opacity_raw=opacity_raw)
+    _call.check_gpu(opacity_raw=opacity_raw)
     return _OpacityEntropy.apply(opacity_raw.contiguous().view(-1), lo, hi)
 
 
-_HOOKED = ("l1_loss", "pearson_corrcoef")
-_saved = {}   # module -> the two originals
+_hook = _call.NameHook(l1_loss=l1_loss, pearson_corrcoef=pearson_corrcoef)
 
 
 def install(train_module):
     """Rebind `l1_loss` and `pearson_corrcoef` in the namespace of the module that holds the training loop (train.py
     looks both up in its globals when called; depth_loss_func reaches pearson_corrcoef the same way). A second install
     is a no-op."""
-    if train_module in _saved:
-        return
-    _saved[train_module] = {name: getattr(train_module, name) for name in _HOOKED}
-    train_module.l1_loss = l1_loss
-    train_module.pearson_corrcoef = pearson_corrcoef
+    _hook.install(train_module)
 
 
 def uninstall(train_module):
     """Restore what install() replaced. Without an install: a no-op."""
-    for name, fn in _saved.pop(train_module, {}).items():
-        setattr(train_module, name, fn)
+    _hook.uninstall(train_module)

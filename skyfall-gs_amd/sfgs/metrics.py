@@ -22,8 +22,8 @@ There is no torch fallback: without the HIP library every operator raises."""
 import numpy as np
 import torch
 
+from . import _call
 from . import _lib as L
-from .loss import _check_gpu, _check_tensor
 
 __all__ = ["view_metrics", "Evaluator", "psnr", "mse", "install", "uninstall", "ROW"]
 
@@ -32,20 +32,14 @@ _L1, _PSNR, _SSIM, _MSE, _PLANE0 = 0, 1, 2, 3, 4
 
 
 def _check_pair(image, gt_image):
-    _check_tensor("image", image, "[C,H,W] with 1 <= C <= 4", lambda t: t.dim() == 3 and t.numel() > 0 and t.shape[0] <= 4)
-    _check_tensor("gt_image", gt_image, f"{tuple(image.shape)} like image", lambda t: t.shape == image.shape)
+    _call.check_tensor("image", image, "[C,H,W] with 1 <= C <= 4", lambda t: t.dim() == 3 and t.numel() > 0 and t.shape[0] <= 4)
+    _call.check_tensor("gt_image", gt_image, f"{tuple(image.shape)} like image", lambda t: t.shape == image.shape)
     return tuple(int(v) for v in image.shape)
 
 
 def _check_row(out):
-    if out is None:
-        return
-    if not isinstance(out, torch.Tensor):
-        raise ValueError("out must be a tensor or None")
-    if out.dtype != torch.float64:
-        raise ValueError(f"out must be float64, got {out.dtype}")
-    if tuple(out.shape) != (8,) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous [8], got {tuple(out.shape)}")
+    _call.check_tensor("out", out, "a contiguous [8]", lambda t: tuple(t.shape) == (8,) and t.is_contiguous(),
+                       dtypes=(torch.float64,), none_ok=True)
 
 
 def _run(a, b, P, H, W, flags, row):
@@ -54,12 +48,8 @@ def _run(a, b, P, H, W, flags, row):
     dev = a.device
     args = L.SfgsMetricsArgs(L.C.sizeof(L.SfgsMetricsArgs), P, H, W, a.data_ptr(), b.data_ptr(), int(flags), 0)
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nbytes = lib.sfgs_metrics_scratch_bytes(L.C.byref(args))
-        if nbytes == 0:
-            raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        L.check(lib.sfgs_metrics_view(L.C.byref(args), L.ptr(row), L.ptr(scratch), nbytes, stream))
+        scratch = _call.scratch(lib.sfgs_metrics_scratch_bytes(L.C.byref(args)), dev, refused_if_zero=True)
+        L.check(lib.sfgs_metrics_view(L.C.byref(args), L.ptr(row), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
     return row
 
 
@@ -73,9 +63,8 @@ def view_metrics(image, gt_image, clamp=True, ssim=True, out=None):
     synchronisation. out: a float64 [8] tensor on the same device to write into (it is returned)."""
     Cc, H, W = _check_pair(image, gt_image)
     _check_row(out)
-    _check_gpu(image=image, gt_image=gt_image)
-    if out is not None and out.device != image.device:
-        raise ValueError(f"out must be on image's device {image.device}, got {out.device}")
+    _call.check_gpu(image=image, gt_image=gt_image)
+    _call.same_device(image.device, "image's device", out=out)
     row = torch.empty(8, dtype=torch.float64, device=image.device) if out is None else out
     return _run(image.detach().contiguous(), gt_image.detach().contiguous(), Cc, H, W, _flags(clamp, ssim), row)
 
@@ -100,11 +89,10 @@ class Evaluator:
         Cc, H, W = _check_pair(image, gt_image)
         if self.n >= self.capacity:
             raise ValueError(f"the Evaluator is full: capacity {self.capacity}")
-        _check_gpu(image=image, gt_image=gt_image)
+        _call.check_gpu(image=image, gt_image=gt_image)
         if self._table is None:
             self._table = torch.empty((self.capacity, 8), dtype=torch.float64, device=self.device or image.device)
-        if image.device != self._table.device:
-            raise ValueError(f"image must be on the Evaluator's device {self._table.device}, got {image.device}")
+        _call.same_device(self._table.device, "the Evaluator's device", image=image)
         _run(image.detach().contiguous(), gt_image.detach().contiguous(), Cc, H, W, _flags(clamp, ssim), self._table[self.n])
         self.n += 1
 
@@ -127,11 +115,11 @@ class Evaluator:
 
 def _stream_planes(name1, img1, name2, img2):
     """The checks of the two drop-ins -> (planes, elements per plane)."""
-    _check_tensor(name1, img1, "a non-empty tensor of at least one dimension", lambda t: t.dim() >= 1 and t.numel() > 0)
-    _check_tensor(name2, img2, f"{tuple(img1.shape)} like {name1}", lambda t: t.shape == img1.shape)
+    _call.check_tensor(name1, img1, "a non-empty tensor of at least one dimension", lambda t: t.dim() >= 1 and t.numel() > 0)
+    _call.check_tensor(name2, img2, f"{tuple(img1.shape)} like {name1}", lambda t: t.shape == img1.shape)
     if img1.shape[0] > 4:
         raise ValueError(f"{name1} must have at most 4 planes (shape[0]), got {tuple(img1.shape)}")
-    _check_gpu(**{name1: img1, name2: img2})
+    _call.check_gpu(**{name1: img1, name2: img2})
     return int(img1.shape[0]), img1.numel() // int(img1.shape[0])
 
 
@@ -153,20 +141,15 @@ def mse(img1, img2):
     return _per_plane(img1, img2, L.METRICS_PLANE_MSE)
 
 
-_NAME = "psnr"
-_saved = {}   # module -> its own psnr
+_hook = _call.NameHook(psnr=psnr)
 
 
 def install(train_module):
     """Rebind `psnr` in the namespace of the module that holds training_report (it looks the name up in the module's
     globals when it calls it). A second install is a no-op; nothing else is patched."""
-    if train_module in _saved:
-        return
-    _saved[train_module] = getattr(train_module, _NAME)
-    setattr(train_module, _NAME, psnr)
+    _hook.install(train_module)
 
 
 def uninstall(train_module):
     """Restore what install() replaced. Without an install: a no-op."""
-    if train_module in _saved:
-        setattr(train_module, _NAME, _saved.pop(train_module))
+    _hook.uninstall(train_module)

@@ -14,6 +14,7 @@ Two ways to use it:
 """
 import torch
 
+from . import _call
 from . import _handles
 
 from . import _lib as L
@@ -32,10 +33,9 @@ class _FusedActivations(torch.autograd.Function):
         opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
         rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             L.check(lib.sfgs_prepass_forward(N, L.ptr(scaling_raw), L.ptr(opacity_raw), L.ptr(rotation_raw),
                                              L.ptr(filter3d), f64_mask(filter3d, opacity_raw), L.ptr(scales),
-                                             L.ptr(opac), L.ptr(rot), stream))
+                                             L.ptr(opac), L.ptr(rot), _call.stream(dev)))
         ctx.save_for_backward(scaling_raw, opacity_raw, rotation_raw, filter3d)
         return scales, opac, rot
 
@@ -53,10 +53,10 @@ class _FusedActivations(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous().float()
         g_scales, g_opac, g_rot = c(g_scales), c(g_opac), c(g_rot)
         with torch.cuda.device(dev):
-            stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             L.check(lib.sfgs_prepass_backward(N, L.ptr(scaling_raw), L.ptr(opacity_raw), L.ptr(rotation_raw),
                                               L.ptr(filter3d), f64_mask(filter3d, opacity_raw), L.ptr(g_scales),
-                                              L.ptr(g_opac), L.ptr(g_rot), L.ptr(gs), L.ptr(go), L.ptr(gr), stream))
+                                              L.ptr(g_opac), L.ptr(g_rot), L.ptr(gs), L.ptr(go), L.ptr(gr),
+                                              _call.stream(dev)))
         return gs, go, gr, None, None
 
 

@@ -17,19 +17,12 @@ this mode.
 There is no torch fallback: without the HIP library every operator raises."""
 import torch
 
+from . import _call
 from . import _lib as L
 
 __all__ = ["resample_gt", "create_offset_gt", "install", "uninstall"]
 
-
-def check_tensor(name, t, shape_text, ok_shape):
-    """float32 tensor of an accepted shape, or ValueError naming the argument (sfgs.loss uses the same check)."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    if not ok_shape(t):
-        raise ValueError(f"{name} must be {shape_text}, got {tuple(t.shape)}")
+check_tensor = _call.check_tensor    # importable from here as before
 
 
 def check_shapes(image, subpixel_offset, mask, name="image"):
@@ -47,6 +40,8 @@ def check_shapes(image, subpixel_offset, mask, name="image"):
 
 def check_devices(image, subpixel_offset, mask, name="image"):
     """After every dtype / shape check, and still before the library is loaded: GPU tensors on one device."""
+    # spelled out, not _call.check_gpu + _call.same_device: at 1024 x 1024 without a mask the call is bound by the host, and
+    # the two keyword-argument calls cost it 0.5 us of 12 (profiles/r13_wrapper_plumbing_ab.txt)
     for n, t in ((name, image), ("subpixel_offset", subpixel_offset), ("mask", mask)):
         if t is not None and not t.is_cuda:
             raise ValueError(f"{n} must be a GPU tensor")
@@ -55,7 +50,7 @@ def check_devices(image, subpixel_offset, mask, name="image"):
             raise ValueError(f"{n} must be on {name}'s device {image.device}, got {t.device}")
 
 
-def _run(image, subpixel_offset, mask, shape):
+def run(image, subpixel_offset, mask, shape):
     """The checked arguments, contiguous -> the resampled [C,H,W] on the current stream of image's device."""
     lib = L.load()
     Cc, H, W = shape
@@ -64,9 +59,8 @@ def _run(image, subpixel_offset, mask, shape):
                               None if mask is None else mask.data_ptr(), 0 if mask is None else mask.numel(),
                               subpixel_offset.data_ptr())
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         out = torch.empty((Cc, H, W), dtype=torch.float32, device=dev)
-        L.check(lib.sfgs_resample_gt(L.C.byref(args), L.ptr(out), stream))
+        L.check(lib.sfgs_resample_gt(L.C.byref(args), L.ptr(out), _call.stream(dev)))
     return out
 
 
@@ -77,8 +71,8 @@ def resample_gt(image, subpixel_offset, mask=None):
     column / row 0, +inf the last one. The result never requires grad (the reference's function is @torch.no_grad())."""
     shape = check_shapes(image, subpixel_offset, mask)
     check_devices(image, subpixel_offset, mask)
-    return _run(image.detach().contiguous(), subpixel_offset.detach().contiguous(),
-                None if mask is None else mask.detach().contiguous(), shape)
+    return run(image.detach().contiguous(), subpixel_offset.detach().contiguous(),
+               None if mask is None else mask.detach().contiguous(), shape)
 
 
 def create_offset_gt(image, offset):
@@ -86,20 +80,15 @@ def create_offset_gt(image, offset):
     return resample_gt(image, offset)
 
 
-_NAME = "create_offset_gt"
-_saved = {}   # module -> its own create_offset_gt
+_hook = _call.NameHook(create_offset_gt=create_offset_gt)
 
 
 def install(train_module):
     """Rebind `create_offset_gt` in the namespace of the module that holds the training loop (train.py looks the name up in
     its globals at :215 and :771). A second install is a no-op; nothing else is patched."""
-    if train_module in _saved:
-        return
-    _saved[train_module] = getattr(train_module, _NAME)
-    setattr(train_module, _NAME, create_offset_gt)
+    _hook.install(train_module)
 
 
 def uninstall(train_module):
     """Restore what install() replaced. Without an install: a no-op."""
-    if train_module in _saved:
-        setattr(train_module, _NAME, _saved.pop(train_module))
+    _hook.uninstall(train_module)

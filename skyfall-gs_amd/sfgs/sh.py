@@ -7,15 +7,12 @@ looks up, so the reference's source stays untouched; semantics are the reference
 sh[..., 3, K], only the first (deg+1)^2 coefficients used, no normalisation / offset / clamp)."""
 import torch
 
+from . import _call
 from . import _handles
 
 from . import _lib as L
 
 __all__ = ["eval_sh", "eval_sh_deferred", "DeferredColor", "materialise", "install", "uninstall"]
-
-
-def _stream(dev):
-    return L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class _EvalSH(torch.autograd.Function):
@@ -24,7 +21,7 @@ class _EvalSH(torch.autograd.Function):
         n, k = sh.shape[0], sh.shape[2]
         out = torch.empty(n, 3, dtype=torch.float32, device=sh.device)
         with torch.cuda.device(sh.device):
-            L.check(L.load().sfgs_sh_eval_forward(n, deg, k, L.ptr(sh), L.ptr(dirs), L.ptr(out), _stream(sh.device)))
+            L.check(L.load().sfgs_sh_eval_forward(n, deg, k, L.ptr(sh), L.ptr(dirs), L.ptr(out), _call.stream(sh.device)))
         ctx.deg = deg
         ctx.save_for_backward(sh, dirs)
         return out
@@ -38,7 +35,7 @@ class _EvalSH(torch.autograd.Function):
         g_dirs = torch.empty_like(dirs) if ctx.needs_input_grad[2] else None
         with torch.cuda.device(sh.device):
             L.check(L.load().sfgs_sh_eval_backward(n, ctx.deg, k, L.ptr(sh), L.ptr(dirs), L.ptr(g_out), L.ptr(g_sh),
-                                                   L.ptr(g_dirs), _stream(sh.device)))
+                                                   L.ptr(g_dirs), _call.stream(sh.device)))
         return None, g_sh, g_dirs
 
 

@@ -317,7 +317,7 @@ def plan_export(settings, inputs, export_capacity=None):
     """Plan THIS rank's Gaussians for the whole frame and export the plan (device tensors with fixed strides):
     dict(N, D, rec[N,12] f32, count[NCB] i32, items[NCB, C, 4] i32, C, max_coarse)."""
     import diff_gauss as dg
-    from sfgs import _lib as L
+    from sfgs import _call, _lib as L
     lib = L.load()
     means3D = dg._f32c(inputs["means3D"], "means3D")
     dev = means3D.device
@@ -334,10 +334,10 @@ def plan_export(settings, inputs, export_capacity=None):
     keep = []
     with torch.cuda.device(dev):
         frame = dg._frame(full, dev, 0 if shs is None else int(shs.shape[1]), keep)
-        stream = dg._stream(dev)
-        gs = L.SfgsGaussians(dg.C_sizeof(L.SfgsGaussians), N, L.ptr(means3D), L.ptr(scales), L.ptr(rotations),
+        stream = _call.stream(dev)
+        gs = L.SfgsGaussians(L.C.sizeof(L.SfgsGaussians), N, L.ptr(means3D), L.ptr(scales), L.ptr(rotations),
                              L.ptr(opacities), L.ptr(colors), L.ptr(shs))
-        sizes = L.SfgsRasterSizes(dg.C_sizeof(L.SfgsRasterSizes))
+        sizes = L.SfgsRasterSizes(L.C.sizeof(L.SfgsRasterSizes))
         L.check(lib.sfgs_raster_sizes(N, W, H, 0, 0, L.C.byref(sizes)))
         ncb = max(int(sizes.coarse_bins), 1)
         cap = int(lib.sfgs_raster_slot_capacity(W, H, 4 * N))
@@ -416,7 +416,7 @@ def render_merged_parts(parts, settings):
     """Merge exported plans (part order = Gaussian order of the concatenated set) and render `settings`' frame / band.
     Returns (color, depth, alpha)."""
     import diff_gauss as dg
-    from sfgs import _lib as L
+    from sfgs import _call, _lib as L
     lib = L.load()
     dev = parts[0]["count"].device
     H, W = int(settings.image_height), int(settings.image_width)
@@ -427,8 +427,8 @@ def render_merged_parts(parts, settings):
     keep = []
     with torch.cuda.device(dev):
         frame = dg._frame(settings._replace(sh_degree=0), dev, 0, keep)   # colours are already in the records
-        stream = dg._stream(dev)
-        sizes = L.SfgsRasterSizes(dg.C_sizeof(L.SfgsRasterSizes))
+        stream = _call.stream(dev)
+        sizes = L.SfgsRasterSizes(L.C.sizeof(L.SfgsRasterSizes))
         cap = int(lib.sfgs_raster_slot_capacity(W, H, D))
         ccap = P * C
         L.check(lib.sfgs_raster_sizes(N, W, H, cap, ccap, L.C.byref(sizes)))

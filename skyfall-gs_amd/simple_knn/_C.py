@@ -3,6 +3,7 @@ nearest other points (reference call site scene/gaussian_model.py:324). Kernels:
 small clouds, Z-curve counting sort + box-pruned search above 32 768 points)."""
 import torch
 
+from sfgs import _call
 from sfgs import _lib as L
 
 __all__ = ["distCUDA2"]
@@ -19,8 +20,7 @@ def distCUDA2(points):
     dev = pts.device
     out = torch.empty(N, dtype=torch.float32, device=dev)
     nbytes = int(lib.sfgs_knn_scratch_bytes(N))     # 0 for small clouds (brute force); the spatial path sorts into scratch
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    scratch = _call.scratch(nbytes, dev) if nbytes else None
     with torch.cuda.device(dev):
-        stream = L.C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(lib.sfgs_knn_dist2(L.ptr(pts), N, L.ptr(out), L.ptr(scratch), nbytes, stream))
+        L.check(lib.sfgs_knn_dist2(L.ptr(pts), N, L.ptr(out), L.ptr(scratch), nbytes, _call.stream(dev)))
     return out

@@ -111,3 +111,25 @@ def test_band_renders_tile_the_full_frame_bit_exactly():
     GaussianRasterizer(base)(**inp)
     from diff_gauss import last_counters
     assert total_dups == last_counters()["num_duplicates"]
+
+
+def test_wrappers_enqueue_on_the_callers_current_stream():
+    """sfgs._call.stream is the handle of the CURRENT stream, and a wrapper built on it (sfgs.metrics.view_metrics) has its
+    result ready once that stream alone is synchronised."""
+    from sfgs import _call
+    from sfgs.metrics import view_metrics
+    dev = torch.device(DEV)
+    gen = torch.Generator().manual_seed(5)
+    image, gt = (torch.rand(3, 16, 16, generator=gen).to(dev) for _ in range(2))
+    want = view_metrics(image, gt).cpu()              # on the default stream; .cpu() waits for it
+    assert (_call.stream(dev).value or 0) == torch.cuda.current_stream(dev).cuda_stream    # c_void_p(0).value is None
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        assert side.cuda_stream != torch.cuda.default_stream(dev).cuda_stream
+        assert _call.stream(dev).value == side.cuda_stream
+        row = view_metrics(image, gt)
+        side.synchronize()                            # this stream only: no device-wide synchronisation
+        got = row.cpu()
+    assert torch.isfinite(want[:7]).all() and torch.isnan(want[7])     # l1, psnr, ssim, mse, three planes; no fourth plane
+    assert torch.equal(got[:7], want[:7]) and torch.isnan(got[7])
