@@ -13,7 +13,7 @@
 //                   (no float atomics: the result is bit-reproducible).
 //
 // Compile with -ffp-contract=off (the forward's alpha/skip decisions must be reproduced exactly; FMA
-// only where spelled fmaf, identically to raster_fwd.hip).
+// only where spelled fmaf, identically to composite_fwd.hip).
 #include "sfgs_internal.h"
 
 // Variants that were built, measured and NOT kept live as patches / A/B files, not in this source (tools/build_variant.sh
@@ -254,7 +254,7 @@ composite_bwd_kernel(KFrame kf, int TX8, int TY8, int SX, int SY, const uint2* _
   __shared__ BwdLds<B> lds_all[BWG_WAVES];
   // wave-uniform: wave index, tile, list range and all loop bounds become SGPRs (scalar loads / branches)
   int tx, ty, lw;
-  if ((unsigned)hdr[HDR_TILE_ORDER] & 2u) {   // this frame's forward left a longest-first order (raster_fwd.hip: tile_order_kernel)
+  if ((unsigned)hdr[HDR_TILE_ORDER] & 2u) {   // this frame's forward left a longest-first order (composite_fwd.hip: tile_order_kernel)
     const unsigned ot = ordered_tile<BWG_WAVES>(order, order_P, lw);
     if (ot == 0xffffffffu) return;
     ty = (int)(ot / (unsigned)TX8); tx = (int)(ot - (unsigned)ty * (unsigned)TX8);

@@ -10,7 +10,7 @@
 //                   the 2D -> 3D chain rule (raster_math.h: preprocess_backward_one).
 //
 // Compile with -ffp-contract=off (the forward's alpha/skip decisions must be reproduced exactly; FMA
-// only where spelled fmaf, identically to raster_fwd.hip).
+// only where spelled fmaf, identically to composite_fwd.hip).
 #include <cstring>
 
 #include "act_math.h"

@@ -1,7 +1,7 @@
 // raster_math.h -- per-Gaussian math of the rasterizer hot path (pure functions, no memory traffic).
 //
 // Everything here is SFGS_HD (= __host__ __device__ under hipcc, nothing under g++) so that the
-// same source is (a) inlined into the gfx950 kernels of raster_fwd.hip / raster_bwd.hip and (b)
+// same source is (a) inlined into the gfx950 kernels of the forward (raster_fwd.hip lists its files) and the backward and (b)
 // compiled by g++ into tests/host_check (CPU "host logic" tests, no GPU needed).
 //
 // Reference behaviour implemented (paths relative to the reference tree; [UPSTREAM] = public
@@ -68,7 +68,7 @@ SFGS_HD int f2i_sat(float v) {
   if (v <= -2147483648.0f) return (-2147483647 - 1);
   return (int)v;
 }
-// ---- the short-list sort's exact 32-bit key (select_sort_kernel, raster_fwd.hip) ------------------------------------------
+// ---- the short-list sort's exact 32-bit key (select_sort_kernel, raster_sort.hip) -----------------------------------------
 // View depths are positive finite floats, so their bit patterns order like their values. Within ONE tile the depths usually span
 // far less than the float range: with rel = depth bits - the tile's smallest depth bits (an integer subtraction, nothing is
 // quantised) and pos = the entry's position in the tile's unsorted list (unique, < 2^pos_bits), the word

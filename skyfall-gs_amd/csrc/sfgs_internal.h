@@ -148,7 +148,7 @@ struct GeomView {
                     //     HDR_BIG_COUNT entries, written only for splats that reach more than BIG_WALK coarse bins
   uint32_t* block_items;  // [NB] two-pass binning: how many coarse items preprocess workgroup b wrote to BinsView::pairs
 };
-constexpr int PAIRS_PER_BLOCK = PRE_BLOCK * 6;   // a thread emits at most BIG_WALK (= 6) items itself (raster_fwd.hip)
+constexpr int PAIRS_PER_BLOCK = PRE_BLOCK * 6;   // a thread emits at most BIG_WALK (= 6) items itself (raster_preprocess.hip)
 // The binning's pair list (96 bytes of address space per Gaussian) lives in the BINS blob, on top of the per-tile item /
 // list arrays that only the render stage writes (BinsView::pairs; ADVICE r3: it used to be part of this blob, which the
 // caller keeps for the backward): 72 bytes per Gaussian here instead of 168.
@@ -333,6 +333,14 @@ __device__ __forceinline__ BinItems bin_items(const uint32_t* __restrict__ line,
 #endif
 
 constexpr int LIST_ALIGN = 64;  // every tile list starts on a multiple of 64 slots (fine_bin_kernel)
+#ifdef __HIPCC__
+// list slots the tiles of a coarse bin with `hits` tile hits can take at most: hits + 16 x 63 (every list starts on a
+// multiple of 64), rounded up to 64. The plan scans it into the bins' bases (raster_binning.hip: bin_base_scan),
+// select_sort_kernel (raster_sort.hip) tests a bin's stretch against the caller's slot capacity with it.
+__device__ __forceinline__ unsigned bin_slots_needed(unsigned hits) {
+  return hits ? ((hits + COARSE_TILES * (LIST_ALIGN - 1) + LIST_ALIGN - 1) & ~(unsigned)(LIST_ALIGN - 1)) : 0u;
+}
+#endif
 
 struct ImageView {
   uint32_t* n_contrib;  // [P] list position (1-based) of the last contributor
@@ -585,6 +593,26 @@ __device__ __forceinline__ unsigned block_excl_scan_u32(unsigned v, unsigned* to
   __syncthreads();
   return res;
 }
+
+// ---- the forward's stages: a translation unit each, every kernel launched from the file that defines it. The entry
+// points of raster_fwd.hip validate, build the views and call these in stream order; each returns an SFGS_* code.
+int check_frame(const SfgsFrame* f);                               // raster_fwd.hip
+hipError_t zero_head(void* p, size_t bytes, hipStream_t stream);   // raster_fwd.hip: clears the head of the tiles blob
+// raster_preprocess.hip: max |subpixel_offset| into the header (plan and merge); subpix_bound + preprocess + big_walk.
+// `two_pass`: the coarse items go to BinsView::pairs (plan_binning moves them) instead of straight into the slabs
+void launch_subpix_bound(const float* subpix, int W, int H, unsigned long long* hdr, hipStream_t stream);
+int plan_preprocess(const SfgsFrame* frame, const SfgsGaussians* g, int32_t* radii, const KFrame& kf, const GeomView& gv,
+                    const TilesView& tv, const BinsView& bv, int64_t dup_capacity, int64_t coarse_capacity, bool two_pass,
+                    hipStream_t stream);
+// raster_binning.hip: bin_count + bin_rank + bin_scatter (two_pass) and the plan's scans
+int plan_binning(const SfgsFrame* frame, int N, const GeomView& gv, const TilesView& tv, const BinsView& bv,
+                 int64_t coarse_capacity, bool two_pass, void* counters_pinned_host, hipStream_t stream);
+// raster_sort.hip: the sorted per-tile lists, by the route the "sort" option / the frame's hints choose
+int sort_tile_lists(const SfgsFrame* frame, const TilesView& tv, const BinsView& bv, int64_t dup_capacity,
+                    int64_t coarse_capacity, int64_t num_duplicates, hipStream_t stream);
+// composite_fwd.hip: tile order (option / hint) + compositing; `iv` = nullptr: no backward will follow
+int composite_forward(const SfgsFrame* frame, const KFrame& kf, const GeomView& gv, const TilesView& tv, const BinsView& bv,
+                      const ImageView* iv, float* out_color, float* out_depth, float* out_alpha, hipStream_t stream);
 
 // composite_bwd.hip (a translation unit of its own: compiled with another scheduling strategy, see the Makefile)
 void launch_composite_bwd(unsigned grid, hipStream_t stream, KFrame kf, int TX8, int TY8, int SX, int SY,

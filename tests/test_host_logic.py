@@ -255,8 +255,32 @@ def test_route_options_are_set_through_the_abi_not_the_environment():
         assert r.stdout.split() == ["split", "never"], r.stdout + r.stderr
     finally:
         del os.environ["SFGS_SORT"]
-    src = "".join(open(os.path.join(ROOT, "skyfall-gs_amd", "csrc", f)).read() for f in ("raster_fwd.hip", "raster_bwd.hip", "composite_bwd.hip", "knn.hip"))
-    assert "getenv" not in src
+    # ... which is the library's ONE look at the environment: the options table of api.cpp, read when the library is loaded.
+    # No other source file of csrc/ calls getenv.
+    calls = {f: open(os.path.join(CSRC, f)).read().count("getenv") for f in _csrc_sources()}
+    assert {f: n for f, n in calls.items() if n} == {"api.cpp": 1}
+
+
+CSRC = os.path.join(ROOT, "skyfall-gs_amd", "csrc")
+
+
+def _csrc_sources():
+    return sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
+
+
+def test_makefile_lists_every_source():
+    """A source file csrc/Makefile does not know would link without its kernels' flags, or not at all: every *.hip / *.cpp of
+    csrc/ is in SRCS, and every file FLAG_FILES or a per-file `CXXFLAGS +=` rule names is one of SRCS."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    var = lambda name: re.search(r"^%s\s*=(.*)$" % name, mk, re.M).group(1).split()
+    srcs = var("SRCS")
+    assert len(srcs) == len(set(srcs))
+    assert sorted(srcs) == _csrc_sources()
+    assert var("FLAG_FILES") and set(var("FLAG_FILES")) <= set(srcs)
+    rules = re.findall(r"^((?:_obj/\S+\.o\s*)+):\s*CXXFLAGS\s*\+=", mk, re.M)
+    named = [t[len("_obj/"):-len(".o")] for r in rules for t in r.split()]
+    assert rules and len(rules) == len(re.findall(r"^_obj/.*CXXFLAGS\s*\+=", mk, re.M))   # every per-file rule was parsed
+    assert set(named) <= set(srcs), sorted(set(named) - set(srcs))
 
 
 def _bench_module():
