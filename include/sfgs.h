@@ -20,6 +20,7 @@
  *   sfgs_metrics_*     the evaluation pass of training_report: clamp, l1_loss, psnr (and ssim)   train.py:1064,1075,1090-1091, utils/image_utils.py:14-19, utils/loss_utils.py:17-18,33-63
  *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
+ *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
  *
@@ -41,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 25
+#define SFGS_ABI_VERSION 26
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -578,6 +579,47 @@ typedef struct SfgsMetricsArgs {
 } SfgsMetricsArgs;
 size_t sfgs_metrics_scratch_bytes(const SfgsMetricsArgs* args);   /* 0: bad arguments (sfgs_last_error) */
 int sfgs_metrics_view(const SfgsMetricsArgs* args, double* row8, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Similarity transform of a Gaussian scene (ABI 26; csrc/transform.hip): x' = s R x + t applied to everything a trained scene
+ * carries that depends on its frame. The reference trains every satellite scene in a frame of its own (readSatelliteInfo,
+ * scene/dataset_readers.py:378-390: rotated by the dataset's R / T, scaled to a 99th-percentile radius of 256, dropped so that
+ * the 1st percentile of z is 0), so two trained tiles differ by a full similarity; this is how they get into one frame.
+ * Per Gaussian, every pair (in, out) optional -- a pair with a NULL `in` is skipped -- and out == in allowed:
+ *     xyz [N][3]        out = s * ((R[0] x + R[1] y) + R[2] z per row of R) + t       (product with s after the dot product)
+ *     scaling [N][3]    SFGS_SIM_SCALING_LOG set: out = in + log_s (the model's _scaling, a fused PLY's scale_*);  clear: out = in * s
+ *     rotation [N][4]   (w, x, y, z), as given, not renormalised: out = q_R (x) q (Hamilton product, q_R on the left)
+ *     sh_rest           sh_rest_coeffs in {0, 3, 8, 15} coefficients per channel beyond DC, [N][K-1][3] (the model's
+ *                       _features_rest) or, with SFGS_SIM_REST_N3K, [N][3][K-1] (a fused PLY's f_rest_* order,
+ *                       scene/gaussian_model.py:461-467): the coefficients of band l = 1, 2, 3 are multiplied by D_l per channel,
+ *                       out_i = sum_j D_l[i][j] in_j, whatever the active degree is
+ *     filter_3D [N][1]  out = in * s
+ * DC colour and opacity do not change (the 3D filter's opacity compensation is scale-invariant) and are not passed. D_l is the
+ * real-SH rotation matrix of band l in the basis order and signs of eval_sh (utils/sh_utils.py:57-112):
+ * eval_sh(D sh, R d) == eval_sh(sh, d) for every unit d. All constants travel by value as float32; the caller forms them in
+ * float64 and rounds once. Arithmetic: float32, products and sums as written, sums in index order from the first term,
+ * nothing contracted; no atomics. ONE launch, no scratch: a workgroup stages the contiguous block of 256 rows of xyz and
+ * sh_rest through LDS (coalesced 16-byte global accesses; a lane then walks its own row at an odd dword stride, which is
+ * conflict-free), scaling and filter_3D are elementwise, a quaternion is one 16-byte access. No profiler id. */
+#define SFGS_SIM_SCALING_LOG 1
+#define SFGS_SIM_REST_N3K 2
+typedef struct SfgsSimilarityArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsSimilarityArgs) */
+  int32_t flags;                 /* SFGS_SIM_* bits */
+  int64_t n;                     /* Gaussians, 0 <= n < 2^31 (0: nothing is launched) */
+  int32_t sh_rest_coeffs;        /* K - 1: 0, 3, 8 or 15 (0: sh_rest is not touched) */
+  int32_t reserved;
+  const float* xyz_in;       float* xyz_out;
+  const float* scaling_in;   float* scaling_out;
+  const float* rotation_in;  float* rotation_out;
+  const float* sh_rest_in;   float* sh_rest_out;
+  const float* filter3d_in;  float* filter3d_out;
+  float R[9];                    /* row-major */
+  float s, log_s;
+  float t[3];
+  float q[4];                    /* the rotation's quaternion (w, x, y, z) */
+  float D1[9], D2[25], D3[49];   /* row-major */
+} SfgsSimilarityArgs;
+int sfgs_similarity_transform(const SfgsSimilarityArgs* args, void* stream);
 
 /* ---- Geometry evaluation (ABI 22; csrc/geometry.hip): evaluate_gs_geometry.py + dsmr.py without their host stages ----------
  * Stage 1, depth map -> height grid (DSM). One call per view into the SAME accumulators; the merged point cloud is never

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -107,6 +107,19 @@ class SfgsMetricsArgs(C.Structure):
 METRICS_CLAMP, METRICS_SSIM, METRICS_PLANE_MSE = 1, 2, 4
 
 
+class SfgsSimilarityArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_int32), ("n", C.c_int64), ("sh_rest_coeffs", C.c_int32),
+                ("reserved", C.c_int32), ("xyz_in", C.c_void_p), ("xyz_out", C.c_void_p), ("scaling_in", C.c_void_p),
+                ("scaling_out", C.c_void_p), ("rotation_in", C.c_void_p), ("rotation_out", C.c_void_p),
+                ("sh_rest_in", C.c_void_p), ("sh_rest_out", C.c_void_p), ("filter3d_in", C.c_void_p),
+                ("filter3d_out", C.c_void_p), ("R", C.c_float * 9), ("s", C.c_float), ("log_s", C.c_float),
+                ("t", C.c_float * 3), ("q", C.c_float * 4), ("D1", C.c_float * 9), ("D2", C.c_float * 25),
+                ("D3", C.c_float * 49)]
+
+
+SIM_SCALING_LOG, SIM_REST_N3K = 1, 2
+
+
 class SfgsDsmViewArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("mask", C.c_void_p),
                 ("M", C.c_double * 9), ("c", C.c_double * 3), ("origin", C.c_double * 3), ("cx_pix", C.c_double),
@@ -180,6 +193,7 @@ SYMBOLS = {
     "sfgs_frame_quantize": (C.c_int, [_V, _I32, _I32, _V, _V]),
     "sfgs_metrics_scratch_bytes": (_SZ, [C.POINTER(SfgsMetricsArgs)]),
     "sfgs_metrics_view": (C.c_int, [C.POINTER(SfgsMetricsArgs), _V, _V, _SZ, _V]),
+    "sfgs_similarity_transform": (C.c_int, [C.POINTER(SfgsSimilarityArgs), _V]),
     "sfgs_dsm_accumulate": (C.c_int, [C.POINTER(SfgsDsmViewArgs), _V, _V, _V, _V]),
     "sfgs_dsm_finalize": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V]),
     "sfgs_dsmr_scratch_bytes": (_SZ, [C.POINTER(SfgsDsmrArgs)]),

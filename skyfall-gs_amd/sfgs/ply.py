@@ -311,11 +311,42 @@ def detect_sh_degree(path):
     return 0 if n_rest == 0 else int(np.sqrt((n_rest / 3) + 1)) - 1
 
 
-def merge_fused_plys(paths, offsets=None, out_path=None):
-    """Concatenate per-scene fused PLYs (save_fused_ply output: no filter_3D column) into one joint scene, each
-    shifted by its world offset [x,y,z] (the reference has no multi-scene merge; the joint scene is what
-    `sfgs.shard.render_joint` renders band-sharded). All files must have the same columns (same SH degree).
-    Returns the merged vertex table; writes it when out_path is given."""
+_TRANSFORM_CHUNK = 1 << 20   # rows per upload of merge_fused_plys(transforms=...): 59 floats a row at degree 3, ~250 MB
+
+
+def _transform_rows(rows, names, sim, device):
+    """rows: float32 [n, columns] view of a fused table's rows (every column float32), changed in place by `sim` on the
+    device (sfgs.transform): x y z, scale_* (log space), rot_*, f_rest_* (channel-major: the "n3k" layout)."""
+    from . import transform
+    col = {n: i for i, n in enumerate(names)}
+    xyz_c = [col[n] for n in ("x", "y", "z")]
+    scale_c = [col[n] for n in sorted((n for n in names if n.startswith("scale_")), key=lambda n: int(n.split("_")[-1]))]
+    rot_c = [col[n] for n in sorted((n for n in names if n.startswith("rot")), key=lambda n: int(n.split("_")[-1]))]
+    rest_c = [col[n] for n in sorted((n for n in names if n.startswith("f_rest_")), key=lambda n: int(n.split("_")[-1]))]
+    if len(scale_c) != 3 or len(rot_c) != 4 or len(rest_c) not in (0, 9, 24, 45):
+        raise ValueError(f"a fused PLY has 3 scale_*, 4 rot_* and 0 / 9 / 24 / 45 f_rest_* columns, got {len(scale_c)}, "
+                         f"{len(rot_c)}, {len(rest_c)}")
+    for a in range(0, len(rows), _TRANSFORM_CHUNK):
+        part = rows[a:a + _TRANSFORM_CHUNK]
+        up = lambda cols: torch.from_numpy(np.ascontiguousarray(part[:, cols])).to(device)
+        xyz, scale, rot = up(xyz_c), up(scale_c), up(rot_c)
+        rest = up(rest_c).reshape(len(part), 3, len(rest_c) // 3) if rest_c else None
+        transform.transform_gaussians(sim, xyz, scale, rot, rest, None, scaling_is_log=True, rest_layout="n3k", inplace=True)
+        for cols, t in ((xyz_c, xyz), (scale_c, scale), (rot_c, rot), (rest_c, rest)):
+            if t is not None:
+                part[:, cols] = t.reshape(len(part), -1).cpu().numpy()
+
+
+def merge_fused_plys(paths, offsets=None, out_path=None, transforms=None, device="cuda"):
+    """Concatenate per-scene fused PLYs (save_fused_ply output: no filter_3D column) into one joint scene (the
+    reference has no multi-scene merge; the joint scene is what `sfgs.shard.render_joint` renders band-sharded). Each file is
+    either shifted by its world offset [x,y,z] (`offsets`: scenes that already share one frame up to a translation; host only)
+    or moved by its own `sfgs.transform.Similarity` (`transforms`: scenes trained by the reference live in per-scene frames,
+    scene/dataset_readers.py:378-390 -- positions, log-scales, quaternions and the SH coefficients beyond DC go through the HIP
+    kernel on `device`, in chunks of bounded size). `offsets` and `transforms` are mutually exclusive. All files must have the
+    same columns (same SH degree). Returns the merged vertex table; writes it when out_path is given."""
+    if offsets is not None and transforms is not None:
+        raise ValueError("offsets and transforms are mutually exclusive")
     tables = [_vertex_table(p) for p in paths]
     if not tables:
         raise ValueError("no input files")
@@ -323,6 +354,24 @@ def merge_fused_plys(paths, offsets=None, out_path=None):
     for p, t in zip(paths, tables):
         if t.dtype.names != names:
             raise ValueError(f"{p}: columns differ from {paths[0]} (different SH degree or filter_3D present?)")
+    if transforms is not None:
+        from .transform import Similarity
+        transforms = list(transforms)
+        if len(transforms) != len(tables):
+            raise ValueError("one transform per file expected")
+        if not all(isinstance(s, Similarity) for s in transforms):
+            raise ValueError("transforms must be sfgs.transform.Similarity objects")
+        if any(tables[0].dtype[n] != np.float32 for n in names):
+            raise ValueError("transforms need a table of float32 columns (save_fused_ply output)")
+        merged = np.concatenate(tables)
+        flat = merged.view(np.float32).reshape(len(merged), len(names))
+        row = 0
+        for t, sim in zip(tables, transforms):
+            _transform_rows(flat[row:row + len(t)], names, sim, device)
+            row += len(t)
+        if out_path is not None:
+            write_ply(out_path, merged)
+        return merged
     if offsets is None:
         offsets = [(0.0, 0.0, 0.0)] * len(tables)
     if len(offsets) != len(tables):
