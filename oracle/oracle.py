@@ -12,13 +12,49 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "liborc.so")
 _lib = None
+# calibration builds of the same source (oracle/Makefile: `make variants`); tests/grad_bounds.py measures against them
+_VARIANT_PATHS = {"accf": os.path.join(_HERE, "_build", "liborc_accf.so"),
+                  "jit": os.path.join(_HERE, "_build", "liborc_jit.so")}
+_variant_libs = {}
+EXPORT_WORDS = 22   # orc_backward_ex: 12 signed accumulators + 10 magnitude sums per Gaussian
+
+
+def _stale(path):
+    src = os.path.join(_HERE, "sfgs_oracle.c")
+    return not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src)
 
 
 def build(force=False):
-    src = os.path.join(_HERE, "sfgs_oracle.c")
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
+    if force or _stale(_LIB_PATH):
         subprocess.check_call(["make", "-C", _HERE, "-s", "-B"])
     return _LIB_PATH
+
+
+def _declare(L):
+    L.orc_forward.restype = C.c_void_p
+    L.orc_forward.argtypes = [C.POINTER(OrcFrame), C.c_int32] + [C.c_void_p] * 10
+    L.orc_backward.restype = C.c_int
+    L.orc_backward.argtypes = [C.c_void_p, C.POINTER(OrcFrame)] + [C.c_void_p] * 17
+    L.orc_backward_ex.restype = C.c_int
+    L.orc_backward_ex.argtypes = [C.c_void_p, C.POINTER(OrcFrame)] + [C.c_void_p] * 18
+    L.orc_free.argtypes = [C.c_void_p]
+    L.orc_get_counts.argtypes = [C.c_void_p, C.c_void_p]
+    L.orc_pixel_margins.restype = None
+    L.orc_pixel_margins.argtypes = [C.c_void_p, C.POINTER(OrcFrame), C.c_void_p]
+    L.orc_get_chain_state.argtypes = [C.c_void_p, C.c_void_p]
+    return L
+
+
+def variant_lib(name):
+    """One of the calibration builds ("accf": float32 sums in reverse order, "jit": every expf scaled by
+    1 +- 2 * 2^-23 max(1, sum of |terms of its argument|)), built on
+    first use. Never a reference: only OracleRender(..., variant=name) in the CPU calibration tests loads it."""
+    if name not in _variant_libs:
+        path = _VARIANT_PATHS[name]
+        if _stale(path):
+            subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "variants"])
+        _variant_libs[name] = _declare(C.CDLL(path))
+    return _variant_libs[name]
 
 
 class OrcFrame(C.Structure):
@@ -32,15 +68,9 @@ def lib():
     global _lib
     if _lib is None:
         build()
-        _lib = C.CDLL(_LIB_PATH)
-        _lib.orc_forward.restype = C.c_void_p
-        _lib.orc_forward.argtypes = [C.POINTER(OrcFrame), C.c_int32] + [C.c_void_p] * 10
+        _lib = _declare(C.CDLL(_LIB_PATH))
         _lib.orc_forward_rows.restype = C.c_void_p
         _lib.orc_forward_rows.argtypes = [C.POINTER(OrcFrame), C.c_int32] + [C.c_void_p] * 10 + [C.c_int32, C.c_int32]
-        _lib.orc_backward.restype = C.c_int
-        _lib.orc_backward.argtypes = [C.c_void_p, C.POINTER(OrcFrame)] + [C.c_void_p] * 17
-        _lib.orc_free.argtypes = [C.c_void_p]
-        _lib.orc_get_counts.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_get_tiles_touched.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_get_n_contrib.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_get_tile_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -73,10 +103,13 @@ def _ptr(a):
 class OracleRender:
     """One forward pass of the oracle; keeps the state the backward needs."""
 
-    def __init__(self, frame, means3D, scales, rotations, opacities, colors_precomp=None, shs=None, tile_rows=None):
+    def __init__(self, frame, means3D, scales, rotations, opacities, colors_precomp=None, shs=None, tile_rows=None,
+                 variant=None):
         """tile_rows = (row0, row1): render only those rows of 16x16 tiles (orc_forward_rows; forward-only checks of very
-        large frames -- every Gaussian is still projected, `radii` is complete; the other pixels stay zero)."""
-        L = lib()
+        large frames -- every Gaussian is still projected, `radii` is complete; the other pixels stay zero).
+        variant: a calibration build (variant_lib) instead of the oracle proper; forward / backward only."""
+        L = self._L = lib() if variant is None else variant_lib(variant)
+        assert variant is None or tile_rows is None
         self.H, self.W = int(frame["H"]), int(frame["W"])
         self.N = int(means3D.shape[0])
         self._keep = dict(means3D=_f32(means3D), scales=_f32(scales), rotations=_f32(rotations),
@@ -134,7 +167,23 @@ class OracleRender:
         lib().orc_get_geom(self._st, _ptr(out))
         return out
 
-    def backward(self, dL_dcolor=None, dL_ddepth=None, dL_dalpha=None):
+    def pixel_margins(self):
+        """[H,W,3] float64: per pixel, the smallest alpha margin, T margin and |power| of orc_decision_margins (1e30
+        where the pixel never reaches the test) -- see orc_pixel_margins."""
+        out = np.zeros((self.H, self.W, 3), np.float64)
+        lib().orc_pixel_margins(self._st, C.byref(self.frame), _ptr(out))
+        return out
+
+    def chain_state(self):
+        """[N,16] float64 of the float32 per-Gaussian state the backward chain reads: a0,b0,c0, tx,ty,tz, cov3d[6],
+        coef, clamped[3]."""
+        out = np.zeros((self.N, 16), np.float64)
+        lib().orc_get_chain_state(self._st, _ptr(out))
+        return out
+
+    def backward(self, dL_dcolor=None, dL_ddepth=None, dL_dalpha=None, export=False):
+        """export=True: also returns, under "_sums", the [N,22] float64 per-Gaussian sums of orc_backward_ex (the twelve
+        signed accumulators, then the ten magnitude sums of the raw terms). The gradients are the same bits either way."""
         k = self._keep
         N = self.N
         g = dict(means3D=np.zeros((N, 3), np.float32), means2D=np.zeros((N, 3), np.float32),
@@ -143,12 +192,16 @@ class OracleRender:
         gcol = np.zeros((N, 3), np.float32) if k["colors"] is not None else None
         gsh = np.zeros((N, self.sh_coeffs, 3), np.float32) if k["shs"] is not None else None
         dc, dd, da = _f32(dL_dcolor), _f32(dL_ddepth), _f32(dL_dalpha)
-        rc = lib().orc_backward(self._st, C.byref(self.frame), _ptr(k["means3D"]), _ptr(k["scales"]),
-                                _ptr(k["rotations"]), _ptr(k["opacities"]), _ptr(k["colors"]), _ptr(k["shs"]),
-                                _ptr(self.alpha), _ptr(dc), _ptr(dd), _ptr(da), _ptr(g["means3D"]),
-                                _ptr(g["means2D"]), _ptr(g["scales"]), _ptr(g["rotations"]),
-                                _ptr(g["opacities"]), _ptr(gcol), _ptr(gsh))
+        sums = np.zeros((N, EXPORT_WORDS), np.float64) if export else None
+        args = (self._st, C.byref(self.frame), _ptr(k["means3D"]), _ptr(k["scales"]),
+                _ptr(k["rotations"]), _ptr(k["opacities"]), _ptr(k["colors"]), _ptr(k["shs"]),
+                _ptr(self.alpha), _ptr(dc), _ptr(dd), _ptr(da), _ptr(g["means3D"]),
+                _ptr(g["means2D"]), _ptr(g["scales"]), _ptr(g["rotations"]),
+                _ptr(g["opacities"]), _ptr(gcol), _ptr(gsh))
+        rc = self._L.orc_backward_ex(*args, _ptr(sums)) if export else self._L.orc_backward(*args)
         assert rc == 0
+        if export:
+            g["_sums"] = sums
         if gcol is not None:
             g["colors_precomp"] = gcol
         if gsh is not None:
@@ -157,7 +210,7 @@ class OracleRender:
 
     def close(self):
         if self._st:
-            lib().orc_free(self._st)
+            self._L.orc_free(self._st)
             self._st = None
 
     def __del__(self):

@@ -80,6 +80,33 @@ static inline int32_t f2i_sat(float v) {
 static inline int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
 static inline int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
 
+/* Calibration variants (tests/grad_bounds.py; built by `make variants`, never used as a reference):
+ *   -DORC_EXP_JITTER=n  every expf of the compositing loops (forward and backward alike) is scaled by
+ *                       1 +- n 2^-23 max(1, M), the sign from a hash of the pixel and the list position, M = the sum of the
+ *                       magnitudes of the exponent's terms (orc_power_mag): stands in for another float32 exponential
+ *                       (n ulp) whose argument is rounded elsewhere (a float32 sum of three terms is off by a few
+ *                       2^-24 M: the exponent of a thin, rotated splat cancels, M >> |power|).
+ *   -DORC_ACC_FLOAT     the per-Gaussian gradient sums are float32, pixels and tiles visited in reverse order, serially
+ *                       (deterministic): stands in for another float32 summation order. */
+/* sum of the magnitudes of the three terms of power = -0.5 (A dx^2 + C dy^2) - B dx dy */
+static inline float orc_power_mag(float ca, float cb, float cc, float dx, float dy) {
+  return 0.5f * (fabsf(ca) * dx * dx + fabsf(cc) * dy * dy) + fabsf(cb * dx * dy);
+}
+#ifdef ORC_EXP_JITTER
+static inline float orc_expf(float p, float pmag, int px, int py, int64_t k) {
+  uint32_t h = (uint32_t)px * 2654435761u ^ (uint32_t)py * 40503u ^ (uint32_t)k * 2246822519u;
+  h ^= h >> 15; h *= 2654435761u; h ^= h >> 13;
+  return expf(p) * (1.0f + ((h & 1u) ? 1.f : -1.f) * (float)(ORC_EXP_JITTER) * 1.1920929e-7f * fmaxf(1.0f, pmag));
+}
+#else
+#define orc_expf(p, pmag, px, py, k) expf(p)
+#endif
+#ifdef ORC_ACC_FLOAT
+typedef float acc_t;
+#else
+typedef double acc_t;
+#endif
+
 /* SH constants: utils/sh_utils.py:26-56 */
 static const float SH_C0 = 0.28209479177387814f;
 static const float SH_C1 = 0.4886025119029199f;
@@ -356,7 +383,7 @@ OrcState* orc_forward_rows(const OrcFrame* f, int32_t N, const float* means3D, c
           float dx = g->mx - sx, dy = g->my - sy;
           float power = -0.5f * (g->ca * dx * dx + g->cc * dy * dy) - g->cb * dx * dy;
           if (power > 0.0f) continue;
-          float alpha = fminf(0.99f, g->op * expf(power));
+          float alpha = fminf(0.99f, g->op * orc_expf(power, orc_power_mag(g->ca, g->cb, g->cc, dx, dy), px, py, k - s));
           if (alpha < 1.0f / 255.0f) continue;
           float test_T = Tr * (1.0f - alpha);
           if (test_T < 0.0001f) break;
@@ -422,6 +449,51 @@ void orc_decision_margins(const OrcState* st, const OrcFrame* f, double out[3]) 
   out[0] = m_alpha; out[1] = m_T; out[2] = m_pow;
 }
 
+/* The same walk, per pixel: out[pix*3 + {0,1,2}] = that pixel's smallest alpha margin, T margin and |power| (1e30 where
+ * the pixel never reaches the test). Unlike the frame form above, a margin here is divided by max(1, M), M = the sum of the
+ * magnitudes of the exponent's terms (orc_power_mag; for T = prod (1 - alpha_j) the sum of alpha_j / (1 - alpha_j)
+ * max(1, M_j) over the factors so far, which is how far those exponentials move the product): another float32
+ * evaluation moves exp(power) by a few 2^-24 max(1, M), relatively, so a thin rotated splat (M in the hundreds) flips a
+ * decision from correspondingly further away. tests/grad_bounds.py zeroes the upstream gradients of the pixels whose
+ * margin is below a threshold: every term a pixel adds to any gradient is linear in them, so such a pixel drops out of
+ * the comparison for every Gaussian of its list at once. */
+void orc_pixel_margins(const OrcState* st, const OrcFrame* f, double* out) {
+  const int W = st->W, H = st->H, TX = st->TX;
+  const int64_t T = (int64_t)st->TX * st->TY;
+#pragma omp parallel for schedule(dynamic, 4)
+  for (int64_t t = 0; t < T; ++t) {
+    int tx0 = (int)(t % TX) * TILE, ty0 = (int)(t / TX) * TILE;
+    int64_t s = st->tile_start[t], e = st->tile_start[t + 1];
+    for (int py = ty0; py < ty0 + TILE && py < H; ++py)
+      for (int px = tx0; px < tx0 + TILE && px < W; ++px) {
+        int64_t pix = (int64_t)py * W + px;
+        float sx = (float)px, sy = (float)py;
+        if (f->subpix) { sx += f->subpix[pix * 2 + 0]; sy += f->subpix[pix * 2 + 1]; }
+        double m_alpha = 1e30, m_T = 1e30, m_pow = 1e30, t_mag = 0.0;
+        float Tr = 1.0f;
+        for (int64_t k = s; k < e; ++k) {
+          const OrcGeom* g = &st->g[st->list[k]];
+          float dx = g->mx - sx, dy = g->my - sy;
+          float power = -0.5f * (g->ca * dx * dx + g->cc * dy * dy) - g->cb * dx * dy;
+          if (fabs((double)power) < m_pow) m_pow = fabs((double)power);
+          if (power > 0.0f) continue;
+          const double gm = fmax(1.0, (double)orc_power_mag(g->ca, g->cb, g->cc, dx, dy));
+          float alpha = fminf(0.99f, g->op * expf(power));
+          double da = fabs((double)alpha * 255.0 - 1.0) / gm;
+          if (da < m_alpha) m_alpha = da;
+          if (alpha < 1.0f / 255.0f) continue;
+          t_mag += gm * (double)alpha / (1.0 - (double)alpha);
+          float test_T = Tr * (1.0f - alpha);
+          double dt = fabs((double)test_T / 1e-4 - 1.0) / fmax(1.0, t_mag);
+          if (dt < m_T) m_T = dt;
+          if (test_T < 0.0001f) break;
+          Tr = test_T;
+        }
+        out[pix * 3 + 0] = m_alpha; out[pix * 3 + 1] = m_T; out[pix * 3 + 2] = m_pow;
+      }
+  }
+}
+
 /* introspection for tests */
 void orc_get_counts(const OrcState* st, int64_t out[4]) {
   int64_t nvis = 0, maxlen = 0;
@@ -458,35 +530,88 @@ void orc_get_geom(const OrcState* st, float* out) {
   }
 }
 
-/* ---- backward: A.6 ----------------------------------------------------------------------- */
-typedef struct Acc2D { double gmx, gmy, absx, absy, gA, gB, gC, gop, grgb[3], gdepth; } Acc2D;
+/* per-Gaussian float32 state that the backward chain reads: [N,16] = a0,b0,c0, tx,ty,tz, cov3d[6], coef, clamped[3] */
+void orc_get_chain_state(const OrcState* st, double* out) {
+  for (int32_t i = 0; i < st->N; ++i) {
+    const OrcGeom* g = &st->g[i];
+    double* o = out + 16 * (size_t)i;
+    o[0] = g->a0; o[1] = g->b0; o[2] = g->c0; o[3] = g->tx; o[4] = g->ty; o[5] = g->tz;
+    for (int k = 0; k < 6; ++k) o[6 + k] = g->cov3d[k];
+    o[12] = g->coef; o[13] = g->clamped[0]; o[14] = g->clamped[1]; o[15] = g->clamped[2];
+  }
+}
 
-static inline void atomic_add_d(double* p, double v) {
+/* ---- backward: A.6 ----------------------------------------------------------------------- */
+typedef struct Acc2D { acc_t gmx, gmy, absx, absy, gA, gB, gC, gop, grgb[3], gdepth; } Acc2D;
+/* magnitude sums of the RAW per-pair terms (orc_backward_ex): u dx, u dy, u dx^2, u dx dy, u dy^2, u, w g_r, w g_g, w g_b,
+ * w g_depth, with u = G dL/dalpha_i taken as a magnitude (every subtraction inside it adds magnitudes; G and w count
+ * max(1, orc_power_mag, the pixel's t_mag) times: the error unit of an exponential whose argument is a float32 sum, and
+ * of a transmittance chain built from such exponentials) */
+#define ORC_NMAG 10
+#define ORC_EXPORT_WORDS (12 + ORC_NMAG)
+typedef struct Mag2D { double m[ORC_NMAG]; } Mag2D;
+
+static inline void atomic_add_d(acc_t* p, acc_t v) {
+#ifndef ORC_ACC_FLOAT
 #pragma omp atomic
+#endif
   *p += v;
 }
+#ifdef ORC_ACC_FLOAT
+static inline void atomic_add_m(double* p, double v) { *p += v; }
+#else
+#define atomic_add_m atomic_add_d
+#endif
+
+int orc_backward_ex(const OrcState* st, const OrcFrame* f, const float* means3D, const float* scales,
+                    const float* rots, const float* opac, const float* colors, const float* shs,
+                    const float* out_alpha, const float* dL_dcolor, const float* dL_ddepth,
+                    const float* dL_dalpha, float* g_means3D, float* g_means2D, float* g_scales,
+                    float* g_rots, float* g_opac, float* g_colors, float* g_shs, double* export_sums);
 
 int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, const float* scales,
                  const float* rots, const float* opac, const float* colors, const float* shs,
                  const float* out_alpha, const float* dL_dcolor, const float* dL_ddepth,
                  const float* dL_dalpha, float* g_means3D, float* g_means2D, float* g_scales,
                  float* g_rots, float* g_opac, float* g_colors, float* g_shs) {
+  return orc_backward_ex(st, f, means3D, scales, rots, opac, colors, shs, out_alpha, dL_dcolor, dL_ddepth, dL_dalpha,
+                         g_means3D, g_means2D, g_scales, g_rots, g_opac, g_colors, g_shs, NULL);
+}
+
+/* export_sums (may be NULL): [N, 22] doubles per Gaussian = the twelve signed accumulators in Acc2D order, then the ten
+ * magnitude sums of Mag2D. The float outputs do not depend on it. */
+int orc_backward_ex(const OrcState* st, const OrcFrame* f, const float* means3D, const float* scales,
+                    const float* rots, const float* opac, const float* colors, const float* shs,
+                    const float* out_alpha, const float* dL_dcolor, const float* dL_ddepth,
+                    const float* dL_dalpha, float* g_means3D, float* g_means2D, float* g_scales,
+                    float* g_rots, float* g_opac, float* g_colors, float* g_shs, double* export_sums) {
   (void)colors; (void)out_alpha;
   const int N = st->N, W = st->W, H = st->H, TX = st->TX, TY = st->TY;
   const int64_t T = (int64_t)TX * TY, P = (int64_t)W * H;
   Acc2D* acc = (Acc2D*)calloc((size_t)(N > 0 ? N : 1), sizeof(Acc2D));
+  Mag2D* mag = export_sums ? (Mag2D*)calloc((size_t)(N > 0 ? N : 1), sizeof(Mag2D)) : NULL;
   const float bg[3] = {f->bg[0], f->bg[1], f->bg[2]};
   const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
 
+#ifdef ORC_ACC_FLOAT
+  for (int64_t t = T - 1; t >= 0; --t) {
+#else
 #pragma omp parallel for schedule(dynamic, 4)
   for (int64_t t = 0; t < T; ++t) {
+#endif
     int tx0 = (int)(t % TX) * TILE, ty0 = (int)(t / TX) * TILE;
     int64_t s = st->tile_start[t], e = st->tile_start[t + 1];
     int64_t L = e - s;
     if (L == 0) continue;
     Acc2D* loc = (Acc2D*)calloc((size_t)L, sizeof(Acc2D));
+    Mag2D* lmag = mag ? (Mag2D*)calloc((size_t)L, sizeof(Mag2D)) : NULL;
+#ifdef ORC_ACC_FLOAT
+    for (int py = imin(ty0 + TILE, H) - 1; py >= ty0; --py)
+      for (int px = imin(tx0 + TILE, W) - 1; px >= tx0; --px) {
+#else
     for (int py = ty0; py < ty0 + TILE && py < H; ++py)
       for (int px = tx0; px < tx0 + TILE && px < W; ++px) {
+#endif
         int64_t pix = (int64_t)py * W + px;
         uint32_t last = st->n_contrib[pix];
         if (last == 0) continue;
@@ -500,19 +625,39 @@ int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, co
         gch[2] = dL_dcolor ? dL_dcolor[2 * P + pix] : 0.f;
         float gdep = dL_ddepth ? dL_ddepth[pix] : 0.f;
         float galp = dL_dalpha ? dL_dalpha[pix] : 0.f;
+        double mgch[5]; /* magnitudes of gch */
         if (f->depth_mode == 0) {
           /* depth = Dacc / a, a = 1 - T_final: fold into raw accumulators (A.6) */
           float a = 1.0f - T_final;
           float Dacc = st->dacc[pix];
           gch[3] = gdep / a;
           gch[4] = galp - gdep * Dacc / (a * a);
+          mgch[4] = fabs((double)galp) + fabs((double)(gdep * Dacc / (a * a)));
         } else {
           gch[3] = gdep;
           gch[4] = galp;
+          mgch[4] = fabs((double)galp);
         }
+        for (int ch = 0; ch < 4; ++ch) mgch[ch] = fabs((double)gch[ch]);
         const float bg_dot = bg[0] * gch[0] + bg[1] * gch[1] + bg[2] * gch[2];
+        const double mbg_dot = fabs((double)bg[0]) * mgch[0] + fabs((double)bg[1]) * mgch[1] + fabs((double)bg[2]) * mgch[2];
         float Tr = T_final;
         float accum[5] = {0, 0, 0, 0, 0}, lastv[5] = {0, 0, 0, 0, 0};
+        double maccum[5] = {0, 0, 0, 0, 0}; /* the accum recurrence on magnitudes */
+        /* how far the pixel's exponentials move its transmittance chain, in units of its value: the sum of
+         * alpha_j / (1 - alpha_j) max(1, M_j) over the blended splats (orc_pixel_margins). T, and with it every term of
+         * the pixel, carries this factor. */
+        double t_mag = 0.0;
+        if (lmag)
+          for (int64_t k = s; k < s + (int64_t)last; ++k) {
+            const OrcGeom* g = &st->g[st->list[k]];
+            float dx = g->mx - sx, dy = g->my - sy;
+            float power = -0.5f * (g->ca * dx * dx + g->cc * dy * dy) - g->cb * dx * dy;
+            if (power > 0.0f) continue;
+            float alpha = fminf(0.99f, g->op * expf(power));
+            if (alpha < 1.0f / 255.0f) continue;
+            t_mag += fmax(1.0, (double)orc_power_mag(g->ca, g->cb, g->cc, dx, dy)) * (double)alpha / (1.0 - (double)alpha);
+          }
         float last_alpha = 0.f;
         for (int64_t k = s + (int64_t)last - 1; k >= s; --k) {
           const uint32_t id = st->list[k];
@@ -520,23 +665,40 @@ int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, co
           float dx = g->mx - sx, dy = g->my - sy;
           float power = -0.5f * (g->ca * dx * dx + g->cc * dy * dy) - g->cb * dx * dy;
           if (power > 0.0f) continue;
-          float G = expf(power);
+          const float pmag = orc_power_mag(g->ca, g->cb, g->cc, dx, dy);
+          float G = orc_expf(power, pmag, px, py, k - s);
           float alpha = fminf(0.99f, g->op * G);
           if (alpha < 1.0f / 255.0f) continue;
           Tr = Tr / (1.0f - alpha);
           const float w = alpha * Tr;
           float val[5] = {g->rgb[0], g->rgb[1], g->rgb[2], g->depth, 1.0f};
           float dL_dalpha_i = 0.f;
+          double m_dalpha = 0.0;
           Acc2D* A = &loc[k - s];
           for (int ch = 0; ch < 5; ++ch) {
+            if (lmag) {
+              maccum[ch] = (double)last_alpha * fabs((double)lastv[ch]) + (1.0 - (double)last_alpha) * maccum[ch];
+              m_dalpha += (fabs((double)val[ch]) + maccum[ch]) * mgch[ch];
+            }
             accum[ch] = last_alpha * lastv[ch] + (1.f - last_alpha) * accum[ch];
             lastv[ch] = val[ch];
             dL_dalpha_i += (val[ch] - accum[ch]) * gch[ch];
           }
-          A->grgb[0] += (double)(w * gch[0]);
-          A->grgb[1] += (double)(w * gch[1]);
-          A->grgb[2] += (double)(w * gch[2]);
-          A->gdepth += (double)(w * gch[3]);
+          if (lmag) {
+            /* exp(p) moves by exp(p) times what p moves by: G and w = alpha T carry max(1, sum of |terms of p|) */
+            const double gm = fmax(fmax(1.0, t_mag), (double)pmag);
+            const double mu = gm * (double)G * (m_dalpha * (double)Tr + (double)T_final / (1.0 - (double)alpha) * mbg_dot);
+            const double ax = fabs((double)dx), ay = fabs((double)dy);
+            double* m = lmag[k - s].m;
+            m[0] += mu * ax; m[1] += mu * ay; m[2] += mu * ax * ax; m[3] += mu * ax * ay; m[4] += mu * ay * ay;
+            m[5] += mu;
+            m[6] += gm * (double)w * mgch[0]; m[7] += gm * (double)w * mgch[1]; m[8] += gm * (double)w * mgch[2];
+            m[9] += gm * (double)w * mgch[3];
+          }
+          A->grgb[0] += (acc_t)(w * gch[0]);
+          A->grgb[1] += (acc_t)(w * gch[1]);
+          A->grgb[2] += (acc_t)(w * gch[2]);
+          A->gdepth += (acc_t)(w * gch[3]);
           dL_dalpha_i *= Tr;
           last_alpha = alpha;
           dL_dalpha_i += (-T_final / (1.f - alpha)) * bg_dot;
@@ -547,17 +709,19 @@ int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, co
           const float dG_ddely = -gdy * g->cc - gdx * g->cb;
           const float gx = dL_dG * dG_ddelx * ddelx_dx;
           const float gy = dL_dG * dG_ddely * ddely_dy;
-          A->gmx += (double)gx; A->gmy += (double)gy;
-          A->absx += (double)fabsf(gx); A->absy += (double)fabsf(gy);
-          A->gA += (double)(-0.5f * gdx * dx * dL_dG);
-          A->gB += (double)(-gdx * dy * dL_dG);
-          A->gC += (double)(-0.5f * gdy * dy * dL_dG);
-          A->gop += (double)(G * dL_dalpha_i);
+          A->gmx += (acc_t)gx; A->gmy += (acc_t)gy;
+          A->absx += (acc_t)fabsf(gx); A->absy += (acc_t)fabsf(gy);
+          A->gA += (acc_t)(-0.5f * gdx * dx * dL_dG);
+          A->gB += (acc_t)(-gdx * dy * dL_dG);
+          A->gC += (acc_t)(-0.5f * gdy * dy * dL_dG);
+          A->gop += (acc_t)(G * dL_dalpha_i);
         }
       }
     for (int64_t k = 0; k < L; ++k) {
       Acc2D* dst = &acc[st->list[s + k]];
       const Acc2D* src = &loc[k];
+      if (lmag)
+        for (int w = 0; w < ORC_NMAG; ++w) atomic_add_m(&mag[st->list[s + k]].m[w], lmag[k].m[w]);
       atomic_add_d(&dst->gmx, src->gmx); atomic_add_d(&dst->gmy, src->gmy);
       atomic_add_d(&dst->absx, src->absx); atomic_add_d(&dst->absy, src->absy);
       atomic_add_d(&dst->gA, src->gA); atomic_add_d(&dst->gB, src->gB);
@@ -566,7 +730,18 @@ int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, co
       atomic_add_d(&dst->grgb[2], src->grgb[2]); atomic_add_d(&dst->gdepth, src->gdepth);
     }
     free(loc);
+    free(lmag);
   }
+  if (export_sums)
+    for (int32_t i = 0; i < N; ++i) {
+      const Acc2D* A = &acc[i];
+      double* o = export_sums + ORC_EXPORT_WORDS * (size_t)i;
+      o[0] = (double)A->gmx; o[1] = (double)A->gmy; o[2] = (double)A->absx; o[3] = (double)A->absy;
+      o[4] = (double)A->gA; o[5] = (double)A->gB; o[6] = (double)A->gC; o[7] = (double)A->gop;
+      o[8] = (double)A->grgb[0]; o[9] = (double)A->grgb[1]; o[10] = (double)A->grgb[2]; o[11] = (double)A->gdepth;
+      for (int w = 0; w < ORC_NMAG; ++w) o[12 + w] = mag[i].m[w];
+    }
+  free(mag);
 
   /* per-Gaussian chain rule */
   const float* V = f->view;
@@ -597,7 +772,7 @@ int orc_backward(const OrcState* st, const OrcFrame* f, const float* means3D, co
 
     /* means2D.grad contract: scene/gaussian_model.py:744-749 (col 2 = abs magnitude) */
     gm2[0] = (float)A->gmx; gm2[1] = (float)A->gmy;
-    gm2[2] = (float)sqrt(A->absx * A->absx + A->absy * A->absy);
+    gm2[2] = (float)sqrt((double)A->absx * (double)A->absx + (double)A->absy * (double)A->absy);
 
     /* opacity' = opacity * coef */
     g_opac[i] = gop_hat * g->coef;

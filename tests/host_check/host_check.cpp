@@ -25,6 +25,12 @@ struct HcFrame {
   const float* campos;
 };
 
+// per-Gaussian number of 8x8-tile duplicates (= gradient records of the backward) of the last hc_render call
+static std::vector<int32_t> g_last_dup_counts;
+void hc_last_dup_counts(int32_t* out, int32_t N) {
+  for (int32_t g = 0; g < N; ++g) out[g] = g < (int32_t)g_last_dup_counts.size() ? g_last_dup_counts[g] : 0;
+}
+
 // counters: [0]=D_eff [1]=D_ref [2]=N_vis [3]=max list
 int hc_render(const HcFrame* hf, int32_t N, const float* means, const float* scales, const float* rots,
               const float* opac, const float* colors, const float* shs, float* out_color, float* out_depth,
@@ -73,6 +79,8 @@ int hc_render(const HcFrame* hf, int32_t N, const float* means, const float* sca
         }
   }
   dupoff[N] = (uint32_t)dup_gauss.size();
+  g_last_dup_counts.resize(N);
+  for (int g = 0; g < N; ++g) g_last_dup_counts[g] = (int32_t)(dupoff[g + 1] - dupoff[g]);
   if (rec_out) for (int g = 0; g < N; ++g) if (radii[g] > 0) memcpy(rec_out + 12 * (size_t)g, &rec[g], 48);
   size_t maxlen = 0;
   for (auto& l : lists) { std::sort(l.begin(), l.end()); maxlen = std::max(maxlen, l.size()); }

@@ -31,6 +31,7 @@ def lib():
         _lib = C.CDLL(_OUT)
         _lib.hc_render.restype = C.c_int
         _lib.hc_render.argtypes = [C.POINTER(HcFrame), C.c_int32] + [C.c_void_p] * 22
+        _lib.hc_last_dup_counts.argtypes = [C.c_void_p, C.c_int32]
         _lib.hc_cov3d.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         _lib.hc_quat_to_R.argtypes = [C.c_void_p, C.c_void_p]
         _lib.hc_sh.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -83,6 +84,9 @@ def render(frame, means3D, scales, rotations, opacities, colors_precomp=None, sh
                      _p(out["counters"]))
     assert rc == 0
     out["grads"] = g
+    # per-Gaussian 8x8-tile duplicates = the number of gradient records the backward sums for it
+    out["dup_counts"] = np.zeros(N, np.int32)
+    L.hc_last_dup_counts(_p(out["dup_counts"]), N)
     return out
 
 
