@@ -20,6 +20,7 @@
  *   sfgs_metrics_*     the evaluation pass of training_report: clamp, l1_loss, psnr (and ssim)   train.py:1064,1075,1090-1091, utils/image_utils.py:14-19, utils/loss_utils.py:17-18,33-63
  *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
+ *   sfgs_pointcloud_*  depth_to_point_cloud per view, np.vstack, the cloud's bounds   evaluate_gs_geometry.py:132-215,776,787-790
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
@@ -42,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 26
+#define SFGS_ABI_VERSION 27
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -691,6 +692,43 @@ int sfgs_dsm_apply_shift(const double* sec, int32_t H, int32_t W, const int32_t*
 size_t sfgs_dsm_metrics_scratch_bytes(int32_t H, int32_t W);   /* 0: bad arguments */
 int sfgs_dsm_metrics(const double* pred, const double* gt, const unsigned char* mask, int32_t H, int32_t W,
                      const int32_t* shift, const double* ab, double* out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- Merged point cloud (ABI 27; csrc/pointcloud.hip): depth_to_point_cloud per view + np.vstack over the views
+ * (evaluate_gs_geometry.py:132-215, :776), the file and the bounds the script prints (:779-790), with no host read per view.
+ * The pixel rule and the float64 arithmetic are stage 1's above (one device function serves both files): a pixel is used when
+ * depth > 0, the depth is finite and the mask is non-zero or NULL; +inf is dropped.
+ * sfgs_pointcloud_append adds ONE view in three launches: per-workgroup counts of used pixels (256 pixels each); one
+ * workgroup scans them exclusively, 1024 at a time with a carry that starts at *state, and advances *state by the view's
+ * count; the scatter pass ranks the used pixels inside each workgroup and writes points[row] = (east, north, up) as float64
+ * and, with colours, colors[row] = three uint8 quantised from image [3][H][W] float32 by sfgs_frame_quantize's rule. Rows keep
+ * the view's row-major pixel order and a view's rows follow the previous view's: points[0 .. n) IS the reference's vstack.
+ * No kernel waits for another workgroup.
+ *   state     device, ONE uint64 the caller zeroes before the first view: the points SEEN so far. A row >= capacity is not
+ *             written but still counted, so *state > capacity tells the caller afterwards which capacity would have sufficed.
+ *   points    device, float64 [capacity][3];  colors: device, uint8 [capacity][3], given exactly when args->image is.
+ *   scratch   sfgs_pointcloud_scratch_bytes bytes for the view's H, W (8 bytes per 256 pixels, at least 48 KiB), 8-byte aligned;
+ *             what it answers for ANY valid H, W is enough for sfgs_pointcloud_bounds.
+ * sfgs_pointcloud_bounds writes out6 = (min east, north, up, max east, north, up) over the min(*state, capacity) stored rows:
+ * per-workgroup partials, folded by one workgroup in a fixed order (no float atomics); a NaN coordinate gives NaN, as numpy's
+ * min / max; an empty cloud gives +inf / -inf.
+ * Every refusal of these entry points is SFGS_E_ARG, made before any GPU work: a NULL pointer, H or W < 1 or H * W > 2^30, a zero
+ * focal length, a negative capacity, a scratch that is too small, a wrong struct_size. No profiler ids. */
+typedef struct SfgsPointCloudViewArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsPointCloudViewArgs) */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel, or NULL */
+  const float* image;            /* device, [3][H][W] float32, or NULL (no colours) */
+  double M[9];                   /* camera-to-world rotation, row-major: world = cam @ M + c */
+  double c[3];                   /* camera centre */
+  double origin[3];              /* added after c (the ENU -> UTM translation); zeros for none */
+  double cx_pix, cy_pix, focal_x, focal_y;
+} SfgsPointCloudViewArgs;
+size_t sfgs_pointcloud_scratch_bytes(int32_t H, int32_t W);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_pointcloud_append(const SfgsPointCloudViewArgs* args, double* points, unsigned char* colors, int64_t capacity,
+                           unsigned long long* state, void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_pointcloud_bounds(const double* points, const unsigned long long* state, int64_t capacity, double* out6, void* scratch,
+                           size_t scratch_bytes, void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

@@ -282,15 +282,7 @@ depthvis_color_kernel(const float* __restrict__ depth, const unsigned char* __re
   }
 }
 
-// (img * 255 + 0.5).clip(0, 255).astype(uint8) in float32; NaN -> 0
-__device__ __forceinline__ unsigned char fq_byte(float v) {
-  float t = v * 255.0f;
-  t = t + 0.5f;
-  if (!(t > 0.f)) return 0;
-  if (t > 255.0f) t = 255.0f;
-  return (unsigned char)(int)t;
-}
-
+// fq_byte, the quantiser itself: sfgs_internal.h (pointcloud.hip colours its rows with it)
 template <bool VEC>
 __global__ void __launch_bounds__(DV_COLOR_THREADS)
 frame_quantize_kernel(const float* __restrict__ image, long long P, unsigned char* __restrict__ out) {

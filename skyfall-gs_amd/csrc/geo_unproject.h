@@ -1,0 +1,37 @@
+// geo_unproject.h -- depth pixel -> world point, the float64 sequence of the reference's depth_to_point_cloud
+// (evaluate_gs_geometry.py:173-204) written ONCE: geometry.hip scatters the point into a height grid, pointcloud.hip stores it.
+// tests/geometry_np.unproject states the same sequence in numpy; both files are held to it bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+namespace sfgs {
+
+struct GeoCamera {
+  double M[9], c[3], origin[3];   // world = cam @ M + c, then + origin as a rounding step of its own
+  double cx_pix, cy_pix, focal_x, focal_y;
+};
+
+// A pixel is used when depth > 0, the depth is finite (NaN fails both comparisons, +inf the second) and the mask byte,
+// if there is a mask, is non-zero. p < H * W is the caller's to check.
+__device__ __forceinline__ bool geo_pixel_used(const float* __restrict__ depth, const unsigned char* __restrict__ mask,
+                                               long long p, float* d) {
+  *d = depth[p];
+  return *d > 0.f && *d < INFINITY && (!mask || mask[p] != 0);
+}
+
+// (east, north, up) of pixel (row, col) at depth d. Products and sums as written, nothing contracted (-ffp-contract=off).
+__device__ __forceinline__ void geo_unproject(const GeoCamera& v, int row, int col, float d, double (&w)[3]) {
+  const double z = (double)d;
+  const double x = ((double)col - v.cx_pix) * z / v.focal_x;
+  const double y = ((double)row - v.cy_pix) * z / v.focal_y;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    double t = x * v.M[j] + y * v.M[3 + j];
+    t = t + z * v.M[6 + j];
+    t = t + v.c[j];
+    w[j] = t + v.origin[j];
+  }
+}
+
+}  // namespace sfgs

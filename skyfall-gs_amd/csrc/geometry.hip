@@ -12,6 +12,7 @@
 // Every index is range-checked before it is used: a grid cell before its atomic, a raster pixel before its load (valnan).
 // The kernels have no profiler ids (the id list of sfgs_profile_kernel_name is closed by the loss kernels).
 #include "sfgs_internal.h"
+#include "geo_unproject.h"
 
 #include <math.h>
 
@@ -30,8 +31,8 @@ __device__ __forceinline__ bool geo_finite(double x) { return fabs(x) < INFINITY
 
 // ---- stage 1: depth -> DSM accumulators ----------------------------------------------------------------------------------------
 struct DsmView {
-  double M[9], c[3], origin[3];
-  double cx_pix, cy_pix, focal_x, focal_y, xoff, yoff_top, res;
+  GeoCamera cam;
+  double xoff, yoff_top, res;
   int H, W, xsize, ysize, radius;
 };
 
@@ -54,20 +55,11 @@ dsm_accumulate_kernel(const float* __restrict__ depth, const unsigned char* __re
   const long long p = (long long)blockIdx.x * GEO_THREADS + threadIdx.x;
   bool landed = false;
   if (p < P) {
-    const float d = depth[p];
-    if (d > 0.f && d < INFINITY && (!mask || mask[p] != 0)) {
+    float d;
+    if (geo_pixel_used(depth, mask, p, &d)) {
       const int row = (int)(p / v.W), col = (int)(p - (long long)row * v.W);
-      const double z = (double)d;
-      const double x = ((double)col - v.cx_pix) * z / v.focal_x;
-      const double y = ((double)row - v.cy_pix) * z / v.focal_y;
       double w[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        double t = x * v.M[j] + y * v.M[3 + j];
-        t = t + z * v.M[6 + j];
-        t = t + v.c[j];
-        w[j] = t + v.origin[j];
-      }
+      geo_unproject(v.cam, row, col, d, w);   // geo_unproject.h: shared with pointcloud.hip
       const double qx = (w[0] - v.xoff) / v.res, qy = (v.yoff_top - w[1]) / v.res;
       // (int) truncates toward zero: (-1, 0) lands in cell 0, as numpy's astype(int) does. NaN fails every comparison.
       if (qx > -1.0 && qx < (double)v.xsize && qy > -1.0 && qy < (double)v.ysize) {
@@ -439,9 +431,9 @@ extern "C" int sfgs_dsm_accumulate(const SfgsDsmViewArgs* a, void* acc, uint32_t
   SFGS_REQUIRE(a->depth && acc && num_points, SFGS_E_ARG, "NULL argument");
   SFGS_REQUIRE(a->mode == SFGS_DSM_MAX || count, SFGS_E_ARG, "mean mode needs the count array");
   DsmView v;
-  for (int i = 0; i < 9; ++i) v.M[i] = a->M[i];
-  for (int i = 0; i < 3; ++i) { v.c[i] = a->c[i]; v.origin[i] = a->origin[i]; }
-  v.cx_pix = a->cx_pix; v.cy_pix = a->cy_pix; v.focal_x = a->focal_x; v.focal_y = a->focal_y;
+  for (int i = 0; i < 9; ++i) v.cam.M[i] = a->M[i];
+  for (int i = 0; i < 3; ++i) { v.cam.c[i] = a->c[i]; v.cam.origin[i] = a->origin[i]; }
+  v.cam.cx_pix = a->cx_pix; v.cam.cy_pix = a->cy_pix; v.cam.focal_x = a->focal_x; v.cam.focal_y = a->focal_y;
   v.xoff = a->xoff; v.yoff_top = a->yoff_top; v.res = a->resolution;
   v.H = a->H; v.W = a->W; v.xsize = a->xsize; v.ysize = a->ysize; v.radius = a->radius;
   hipStream_t stream = (hipStream_t)stream_;

@@ -564,6 +564,15 @@ __device__ __forceinline__ void store_sh_rows(float* __restrict__ first, float* 
 // ---- small wave / block primitives ---------------------------------------------------------------
 __device__ __forceinline__ unsigned lane_id() { return __lane_id(); }
 
+// sfgs_frame_quantize's rule for one value: (img * 255 + 0.5).clip(0, 255).astype(uint8) in float32; NaN -> 0
+__device__ __forceinline__ unsigned char fq_byte(float v) {
+  float t = v * 255.0f;
+  t = t + 0.5f;
+  if (!(t > 0.f)) return 0;
+  if (t > 255.0f) t = 255.0f;
+  return (unsigned char)(int)t;
+}
+
 __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
   const unsigned lane = lane_id();
 #pragma unroll

@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -137,6 +137,12 @@ class SfgsDsmrArgs(C.Structure):
 DSM_MAX, DSM_MEAN = 0, 1
 
 
+class SfgsPointCloudViewArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("mask", C.c_void_p),
+                ("image", C.c_void_p), ("M", C.c_double * 9), ("c", C.c_double * 3), ("origin", C.c_double * 3),
+                ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double)]
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -201,6 +207,9 @@ SYMBOLS = {
     "sfgs_dsm_apply_shift": (C.c_int, [_V, _I32, _I32, _V, _V, _V, _V]),
     "sfgs_dsm_metrics_scratch_bytes": (_SZ, [_I32, _I32]),
     "sfgs_dsm_metrics": (C.c_int, [_V, _V, _V, _I32, _I32, _V, _V, _V, _V, _SZ, _V]),
+    "sfgs_pointcloud_scratch_bytes": (_SZ, [_I32, _I32]),
+    "sfgs_pointcloud_append": (C.c_int, [C.POINTER(SfgsPointCloudViewArgs), _V, _V, _I64, _V, _V, _SZ, _V]),
+    "sfgs_pointcloud_bounds": (C.c_int, [_V, _V, _I64, _V, _V, _SZ, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),

@@ -3,8 +3,8 @@
 altitude MAE / RMSE / completeness, with one host read at the end.
 
     acc = DsmAccumulator(DsmGrid.from_metadata(np.loadtxt("JAX_068_DSM.txt")), mode="max", device="cuda")
-    for cam in cameras:                                   # the merged point cloud is never formed
-        acc.add_view(render(cam)["render_depth"], cam, origin=(utm_x, utm_y, alt))
+    for cam in cameras:                                   # the DSM needs no point cloud in between; the merged cloud the
+        acc.add_view(render(cam)["render_depth"], cam, origin=(utm_x, utm_y, alt))   # script also saves: sfgs.pointcloud
     shift = register(gt_dsm, acc.result())                # dsmr.compute_shift(gt, pred, scaling=False) on the device
     m = dsm_metrics(acc.result(), gt_dsm, shift=shift, mask=cls != 9)
     report = evaluate_dsm(depths, cameras, grid, gt_dsm, origin=...)     # the three stages chained, Python numbers out
@@ -83,6 +83,28 @@ def _vec(x, n, name):
     return a
 
 
+def _check_view(device, depth, R, T, focal_x, focal_y, cx, cy, origin, mask, centre_from_view=False, **more_on_device):
+    """The checks of one view (DsmAccumulator.add_depth, PointCloud.add_depth), host checks first, and the camera as the
+    library takes it -> (H, W, (M[9], c[3], origin[3], cx_pix, cy_pix, focal_x, focal_y)); all numbers formed in float64.
+    centre_from_view: form c = -(M T) from the transposed VIEW of R, as tests/geometry_np.unproject does, instead of from a
+    contiguous copy. The last bit of numpy's matrix product depends on the operand's memory order (1 ulp of c, measured);
+    the DSM keeps the copy it always used, the point cloud -- held to that restatement bit for bit -- the view."""
+    H, W = _call.check_depth_map(depth)
+    _call.check_pixel_mask(mask, H, W)
+    R = _vec(R, 9, "R").reshape(3, 3)
+    T = _vec(T, 3, "T")
+    org = np.zeros(3) if origin is None else _vec(origin, 3, "origin")
+    fx, fy, cx, cy = (float(v) for v in (focal_x, focal_y, cx, cy))
+    if not (np.isfinite([fx, fy, cx, cy]).all() and fx != 0 and fy != 0):
+        raise ValueError(f"focal_x, focal_y must be finite and non-zero, cx, cy finite: got {fx}, {fy}, {cx}, {cy}")
+    _call.check_gpu(depth=depth)
+    _call.same_device(device, "device", depth=depth, mask=mask, **more_on_device)
+    M = np.ascontiguousarray(R.T)                     # evaluate_gs_geometry.py:198-201
+    c = -(R.T if centre_from_view else M) @ T
+    return H, W, ((L.C.c_double * 9)(*M.reshape(-1)), (L.C.c_double * 3)(*c), (L.C.c_double * 3)(*org),
+                  cx / 2 * W + W / 2, cy / 2 * H + H / 2, fx, fy)
+
+
 class DsmAccumulator:
     """Height grid that depth maps are scattered into, view after view (csrc/geometry.hip, stage 1).
     mode="max": the maximum height per cell (the reference's create_dsm_manual_satnerf_style); exact and order independent.
@@ -116,25 +138,12 @@ class DsmAccumulator:
         attributes of the reference's Camera (world-to-camera; cx, cy in normalised units); origin: the three numbers
         enu_to_utm_coordinates adds (UTM easting, northing, altitude of the ENU origin) or None; mask: bool / uint8, non-zero =
         use the pixel."""
-        H, W = _call.check_depth_map(depth)
-        _call.check_pixel_mask(mask, H, W)
-        R = _vec(R, 9, "R").reshape(3, 3)
-        T = _vec(T, 3, "T")
-        org = np.zeros(3) if origin is None else _vec(origin, 3, "origin")
-        fx, fy, cx, cy = (float(v) for v in (focal_x, focal_y, cx, cy))
-        if not (np.isfinite([fx, fy, cx, cy]).all() and fx != 0 and fy != 0):
-            raise ValueError(f"focal_x, focal_y must be finite and non-zero, cx, cy finite: got {fx}, {fy}, {cx}, {cy}")
-        _call.check_gpu(depth=depth)
-        _call.same_device(self.device, "device", depth=depth, mask=mask)
-        M = np.ascontiguousarray(R.T)                     # evaluate_gs_geometry.py:198-201
-        c = -M @ T
+        H, W, cam = _check_view(self.device, depth, R, T, focal_x, focal_y, cx, cy, origin, mask)
         lib = L.load()
         depth, mask = depth.detach().contiguous(), _u8(mask)
         g = self.grid
         args = L.SfgsDsmViewArgs(L.C.sizeof(L.SfgsDsmViewArgs), H, W, depth.data_ptr(), None if mask is None else mask.data_ptr(),
-                                 (L.C.c_double * 9)(*M.reshape(-1)), (L.C.c_double * 3)(*c), (L.C.c_double * 3)(*org),
-                                 cx / 2 * W + W / 2, cy / 2 * H + H / 2, fx, fy, g.xoff, g.yoff_top, g.resolution, g.xsize,
-                                 g.ysize, _MODES[self.mode], self.radius)
+                                 *cam, g.xoff, g.yoff_top, g.resolution, g.xsize, g.ysize, _MODES[self.mode], self.radius)
         with torch.cuda.device(self.device):
             L.check(lib.sfgs_dsm_accumulate(L.C.byref(args), L.ptr(self._acc), L.ptr(self._count), L.ptr(self._num),
                                             _call.stream(self.device)))
@@ -257,11 +266,18 @@ def register_simple(pred, gt):
     return _metrics_raw(pred, gt, None, None)[4]
 
 
-def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mode="max", irange=5, radius=1, view_masks=None):
+def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mode="max", irange=5, radius=1, view_masks=None,
+                 cloud=None):
     """The whole chain with ONE host read: scatter every depth map into a DSM, blank the cells keep_mask excludes, register
     the DSM on gt_dsm (scaling off, as the reference calls dsmr), compare -> dict of Python numbers: mae, rmse, valid_pixels,
-    completeness, dx_offset, dy_offset, dz_offset, total_points. gt_dsm: [grid.ysize, grid.xsize] on the GPU."""
+    completeness, dx_offset, dy_offset, dz_offset, total_points. gt_dsm: [grid.ysize, grid.xsize] on the GPU.
+    cloud: a sfgs.pointcloud.PointCloud that every view is appended to as well (same pixels, same order, no host read), for
+    the script's merged PLY and its bounds; the report does not depend on it."""
     depths, cameras = list(depths), list(cameras)
+    if cloud is not None:
+        from .pointcloud import PointCloud
+        if not isinstance(cloud, PointCloud):
+            raise ValueError("cloud must be a sfgs.pointcloud.PointCloud or None")
     if len(depths) != len(cameras) or not depths:
         raise ValueError(f"{len(depths)} depth maps for {len(cameras)} cameras")
     if view_masks is not None and len(view_masks) != len(depths):
@@ -273,6 +289,8 @@ def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mod
     acc = DsmAccumulator(grid, mode=mode, radius=radius, device=gt_dsm.device)
     for k, (depth, cam) in enumerate(zip(depths, cameras)):
         acc.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])
+        if cloud is not None:
+            cloud.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])
     pred = acc.result()
     if keep_mask is not None:                             # evaluate_gs_geometry.py:455-469: water cells are NaN before dsmr
         keep = keep_mask.reshape(grid.ysize, grid.xsize) != 0
