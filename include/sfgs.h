@@ -21,6 +21,7 @@
  *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
  *   sfgs_pointcloud_*  depth_to_point_cloud per view, np.vstack, the cloud's bounds   evaluate_gs_geometry.py:132-215,776,787-790
+ *   sfgs_raster_blend_stats, sfgs_blend_stats_views  (no counterpart: the reference's only pruning tool is GaussianModel.prune_by_radius, scene/gaussian_model.py:752, by distance)
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
  *   sfgs_prepass_*     GaussianModel.get_*_with_3D_filter/get_rotation  scene/gaussian_model.py:207-249 (next row)
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SFGS_ABI_VERSION 27
+#define SFGS_ABI_VERSION 28
 
 typedef enum SfgsStatus {
   SFGS_OK = 0,
@@ -729,6 +730,36 @@ int sfgs_pointcloud_append(const SfgsPointCloudViewArgs* args, double* points, u
                            unsigned long long* state, void* scratch, size_t scratch_bytes, void* stream);
 int sfgs_pointcloud_bounds(const double* points, const unsigned long long* state, int64_t capacity, double* out6, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
+ * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the
+ * per-pixel tests, before the pixel saturated -- with blend weight w = alpha T:
+ *   weight_sum_q32[g] += floor(w 2^32)   (w <= 0.99; an integer sum: exact, the same bits in any order; sum w = q 2^-32)
+ *   hits[g]           += 1
+ *   weight_max[g]      = max(weight_max[g], w)
+ * sfgs_raster_blend_stats runs on the blobs of a FINISHED sfgs_raster_forward_render of the same frame (same N, capacities,
+ * tile-row band), on the same stream: it re-walks the per-tile lists with the forward's own per-pixel functions, in list
+ * order, so every decision, T and w are those of the image, bit for bit. It ADDS into the caller's tables (zero them before
+ * the first view). One launch, three integer atomics per (tile, Gaussian with a blended pixel); no float atomics: two runs
+ * give the same bits.
+ *   pixel_mask  device [H][W], one byte per pixel, or NULL: pairs of pixels whose byte is 0 are not counted (the pixel still
+ *               composites: its transmittance is its own).
+ * sfgs_blend_stats_views, once per view after it: if (hits[i] != hits_seen[i]) { ++views[i]; hits_seen[i] = hits[i]; } --
+ * the number of views a Gaussian was blended in (hits_seen, views: caller-owned, zeroed with the tables).
+ * Refusals are SFGS_E_ARG / SFGS_E_CAPACITY, made before any GPU work: a NULL pointer, a wrong struct_size, N < 0,
+ * out->N != N, a bins blob smaller than the render stage's. N == 0 launches nothing. No profiler ids. */
+typedef struct SfgsBlendStats {
+  uint32_t struct_size;                 /* = sizeof(SfgsBlendStats) */
+  int32_t N;                            /* rows of the three tables = the scene's Gaussians */
+  unsigned long long* weight_sum_q32;   /* device [N]: sum of floor(w * 2^32) */
+  unsigned long long* hits;             /* device [N]: blended (pixel, Gaussian) pairs */
+  float* weight_max;                    /* device [N]: max w (>= 0) */
+} SfgsBlendStats;
+int sfgs_raster_blend_stats(const SfgsFrame* frame, int32_t N, const void* geom, const void* tiles, const void* bins,
+                            size_t bins_bytes, int64_t dup_capacity, int64_t coarse_capacity, const unsigned char* pixel_mask,
+                            const SfgsBlendStats* out, void* stream);
+int sfgs_blend_stats_views(int32_t N, const unsigned long long* hits, unsigned long long* hits_seen, uint32_t* views,
+                           void* stream);
 
 /* Joint render with the Gaussians sharded over ranks (SURVEY 8e "all-gather the preprocessed 2D records"; the reference
  * has no multi-scene render). Every rank runs sfgs_raster_forward_plan on ITS Gaussians for the whole frame, then:

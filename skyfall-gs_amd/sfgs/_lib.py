@@ -6,7 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGS_LIB") or os.path.join(_HERE, "libsfgs.so")   # SFGS_LIB: experiment builds (tools/)
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 SFGS_OK = 0
 DEPTH_NORMALISED, DEPTH_RAW = 0, 1
@@ -143,6 +143,11 @@ class SfgsPointCloudViewArgs(C.Structure):
                 ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double)]
 
 
+class SfgsBlendStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("N", C.c_int32), ("weight_sum_q32", C.c_void_p), ("hits", C.c_void_p),
+                ("weight_max", C.c_void_p)]
+
+
 class SfgsRasterCounters(C.Structure):
     _fields_ = [("num_duplicates", C.c_int64), ("num_duplicates_ref", C.c_int64), ("num_visible", C.c_int64),
                 ("max_tile_list", C.c_int64), ("overflow", C.c_int64), ("max_coarse_bin", C.c_int64),
@@ -210,6 +215,9 @@ SYMBOLS = {
     "sfgs_pointcloud_scratch_bytes": (_SZ, [_I32, _I32]),
     "sfgs_pointcloud_append": (C.c_int, [C.POINTER(SfgsPointCloudViewArgs), _V, _V, _I64, _V, _V, _SZ, _V]),
     "sfgs_pointcloud_bounds": (C.c_int, [_V, _V, _I64, _V, _V, _SZ, _V]),
+    "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
+                                           C.POINTER(SfgsBlendStats), _V]),
+    "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),
     "sfgs_knn_scratch_bytes": (_SZ, [_I32]),
     "sfgs_knn_dist2": (C.c_int, [_V, _I32, _V, _V, _SZ, _V]),
     "sfgs_filter3d_scratch_bytes": (_SZ, [_I32]),

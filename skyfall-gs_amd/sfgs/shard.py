@@ -313,9 +313,12 @@ def render_joint(rasterizer_cls, settings, inputs, height, shard_gaussians=False
 
 
 # ---- Gaussian-sharded joint render: plan locally, exchange, merge, render the band --------------------------------------
-def plan_export(settings, inputs, export_capacity=None):
-    """Plan THIS rank's Gaussians for the whole frame and export the plan (device tensors with fixed strides):
-    dict(N, D, rec[N,12] f32, count[NCB] i32, items[NCB, C, 4] i32, C, max_coarse)."""
+def plan_frame(settings, inputs):
+    """Plan `inputs` (the keyword tensors of GaussianRasterizer.forward, plain float32) for `settings`' frame -- its tile-row
+    band when it has one -- into blobs of its own, growing the capacities until the plan fits. Returns a dict: frame (the
+    SfgsFrame), keep (the tensors it points into), stream, N, W, H, cap, ccap (the capacities the plan ran with), ncb, geom,
+    tiles, bins, radii, D, cmax, counters, inputs (the contiguous tensors the plan read). The caller runs the stages that
+    follow inside `torch.cuda.device(means3D.device)`, on `stream`."""
     import diff_gauss as dg
     from sfgs import _call, _lib as L
     lib = L.load()
@@ -330,10 +333,9 @@ def plan_export(settings, inputs, export_capacity=None):
     if (shs is None) == (colors is None):
         raise ValueError("Please provide exactly one of either SHs or precomputed colors!")
     H, W = int(settings.image_height), int(settings.image_width)
-    full = settings._replace(tile_rows=None)      # the plan covers the whole frame: every band needs these items
     keep = []
     with torch.cuda.device(dev):
-        frame = dg._frame(full, dev, 0 if shs is None else int(shs.shape[1]), keep)
+        frame = dg._frame(settings, dev, 0 if shs is None else int(shs.shape[1]), keep)
         stream = _call.stream(dev)
         gs = L.SfgsGaussians(L.C.sizeof(L.SfgsGaussians), N, L.ptr(means3D), L.ptr(scales), L.ptr(rotations),
                              L.ptr(opacities), L.ptr(colors), L.ptr(shs))
@@ -363,6 +365,22 @@ def plan_export(settings, inputs, export_capacity=None):
             if (new_cap, new_ccap) == (cap, ccap):
                 new_cap = cap * 2        # a duplicate-index pool ran over although the total fits: more room per pool
             cap, ccap = new_cap, new_ccap
+    return dict(frame=frame, keep=keep, stream=stream, N=N, W=W, H=H, cap=cap, ccap=ccap, ncb=ncb, geom=geom, tiles=tiles,
+                bins=bins, radii=radii, D=D, cmax=cmax, counters=cnt,
+                inputs=(means3D, scales, rotations, opacities, colors, shs))
+
+
+def plan_export(settings, inputs, export_capacity=None):
+    """Plan THIS rank's Gaussians for the whole frame and export the plan (device tensors with fixed strides):
+    dict(N, D, rec[N,12] f32, count[NCB] i32, items[NCB, C, 4] i32, C, max_coarse)."""
+    from sfgs import _lib as L
+    lib = L.load()
+    # the plan covers the whole frame: every band needs these items
+    p = plan_frame(settings._replace(tile_rows=None), inputs)
+    frame, stream, N, D, cap, ccap, ncb = p["frame"], p["stream"], p["N"], p["D"], p["cap"], p["ccap"], p["ncb"]
+    geom, tiles, bins, cnt, cmax = p["geom"], p["tiles"], p["bins"], p["counters"], p["cmax"]
+    dev = geom.device
+    with torch.cuda.device(dev):
         cmax = max(cmax, int(cnt.max_bin_items))      # the export carries ALL items of a bin (slab + bin-sorted run)
         if export_capacity is None:
             export_capacity = _agree_max(max(cmax, 1), dev)
