@@ -21,6 +21,7 @@
  *   sfgs_dsm_*         depth_to_point_cloud + create_dsm_manual_satnerf_style, compute_dsm_metrics, register_dsms_simple   evaluate_gs_geometry.py:132-215,270-312,528-585
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
  *   sfgs_pointcloud_*  depth_to_point_cloud per view, np.vstack, the cloud's bounds   evaluate_gs_geometry.py:132-215,776,787-790
+ *   sfgs_ortho_*       (no counterpart: the script renders RGB per camera next to the depth, writes it to a PNG and keeps no georeferenced colour)   evaluate_gs_geometry.py:736-765
  *   sfgs_raster_blend_stats, sfgs_blend_stats_views  (no counterpart: the reference's only pruning tool is GaussianModel.prune_by_radius, scene/gaussian_model.py:752, by distance)
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
@@ -730,6 +731,45 @@ int sfgs_pointcloud_append(const SfgsPointCloudViewArgs* args, double* points, u
                            unsigned long long* state, void* scratch, size_t scratch_bytes, void* stream);
 int sfgs_pointcloud_bounds(const double* points, const unsigned long long* state, int64_t capacity, double* out6, void* scratch,
                            size_t scratch_bytes, void* stream);
+
+/* ---- True orthophoto on the DSM's grid (added under ABI 28: new symbols only; csrc/ortho.hip; Python: sfgs.ortho): per cell
+ * the colour of the HIGHEST point the views put there. The pixel rule, the float64 arithmetic and the cell rule are stage 1's
+ * of the geometry evaluation above (one device function each serves both files), so with the same camera numbers the cells
+ * agree with SFGS_DSM_MAX's bit for bit. One call per view into the SAME accumulator:
+ *   acc   device, uint64 [ysize][xsize], zeroed by the caller; 0 = empty. Every landed point takes a 64-bit integer atomic max with
+ *         bits 63-32  K32(float32(up)): float32() rounds the float64 height to nearest even; on its bit pattern b,
+ *                     K32(b) = (b >> 31) ? ~b : (b | 0x80000000) -- order preserving, and no number maps to 0
+ *         bits 31-24, 23-16, 15-8   r, g, b of the pixel from image [3][H][W] by the frame quantiser's rule
+ *                     (float32 v * 255 + 0.5, clip to 0 ... 255, truncate, NaN -> 0)
+ *         bits 7-0    the view's tag, 1 ... 255
+ *         The winner of a cell is the maximum over (float32 height, r, g, b, tag), lexicographically: heights that differ
+ *         only below float32 resolution tie and colour decides, then the tag. Rounding is monotone, so the winner's height is
+ *         float32(SFGS_DSM_MAX's height) in every cell. A point whose float64 height is not finite is dropped.
+ *   *num_points (device, uint64) counts the points that landed. Integer atomics only: any view order gives the same bits.
+ * The resolve call, ONE launch, unpacks acc; with fill r = 1 ... 3 an EMPTY cell takes the maximum key among the non-empty
+ * cells of its (2r + 1)^2 window clipped to the grid (a single pass: donated values do not propagate):
+ *   rgb      uint8 [ysize][xsize][3], 0 where empty        height  float32 [ysize][xsize], NaN where empty
+ *   source   uint8 [ysize][xsize]: the winning tag, 0 where empty       state  uint8 [ysize][xsize]: 0 empty, 1 own, 2 donated
+ *   coverage uint64 [256], zeroed by the caller (the call ADDS): [0] cells still empty, [t] cells coloured by tag t, own or donated
+ * Limits, status codes and messages are those of the two DSM entry points; a tag outside 1 ... 255 and a fill outside
+ * 0 ... 3 are SFGS_E_ARG. No profiler ids. */
+typedef struct SfgsOrthoViewArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsOrthoViewArgs) */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel, or NULL */
+  double M[9];                   /* camera-to-world rotation, row-major: world = cam @ M + c */
+  double c[3];                   /* camera centre */
+  double origin[3];              /* added after c (the ENU -> UTM translation); zeros for none */
+  double cx_pix, cy_pix, focal_x, focal_y;
+  double xoff, yoff_top, resolution;
+  int32_t xsize, ysize;          /* > 0, xsize * ysize <= 2^28 */
+  const float* image;            /* device, [3][H][W] float32 */
+  int32_t tag;                   /* 1 ... 255 */
+} SfgsOrthoViewArgs;
+int sfgs_ortho_accumulate(const SfgsOrthoViewArgs* args, void* acc, unsigned long long* num_points, void* stream);
+int sfgs_ortho_resolve(int32_t xsize, int32_t ysize, int32_t fill, const void* acc, unsigned char* rgb, float* height,
+                       unsigned char* source, unsigned char* state, unsigned long long* coverage, void* stream);
 
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the

@@ -1,5 +1,6 @@
 // geo_unproject.h -- depth pixel -> world point, the float64 sequence of the reference's depth_to_point_cloud
-// (evaluate_gs_geometry.py:173-204) written ONCE: geometry.hip scatters the point into a height grid, pointcloud.hip stores it.
+// (evaluate_gs_geometry.py:173-204) written ONCE: geometry.hip scatters the point into a height grid, pointcloud.hip stores it,
+// ortho.hip scatters its height and colour into the same grid (geo_cell: the cell rule, also written once).
 // tests/geometry_np.unproject states the same sequence in numpy; both files are held to it bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +33,22 @@ __device__ __forceinline__ void geo_unproject(const GeoCamera& v, int row, int c
     t = t + v.c[j];
     w[j] = t + v.origin[j];
   }
+}
+
+// The grid cell of a world point: geometry.hip's height grid and ortho.hip's colour grid are held to each other cell for cell.
+// (int) truncates toward zero: (-1, 0) lands in cell 0, as numpy's astype(int) does. NaN fails every comparison. The open
+// interval is tested on the float64 first (a value beyond int's range is never converted), the integer range after it.
+__device__ __forceinline__ bool geo_cell(double east, double north, double xoff, double yoff_top, double res, int xsize, int ysize,
+                                         int* gx_out, int* gy_out) {
+  const double qx = (east - xoff) / res, qy = (yoff_top - north) / res;
+  if (qx > -1.0 && qx < (double)xsize && qy > -1.0 && qy < (double)ysize) {
+    const int gx = (int)qx, gy = (int)qy;
+    if (gx >= 0 && gx < xsize && gy >= 0 && gy < ysize) {
+      *gx_out = gx; *gy_out = gy;
+      return true;
+    }
+  }
+  return false;
 }
 
 }  // namespace sfgs

@@ -60,26 +60,22 @@ dsm_accumulate_kernel(const float* __restrict__ depth, const unsigned char* __re
       const int row = (int)(p / v.W), col = (int)(p - (long long)row * v.W);
       double w[3];
       geo_unproject(v.cam, row, col, d, w);   // geo_unproject.h: shared with pointcloud.hip
-      const double qx = (w[0] - v.xoff) / v.res, qy = (v.yoff_top - w[1]) / v.res;
-      // (int) truncates toward zero: (-1, 0) lands in cell 0, as numpy's astype(int) does. NaN fails every comparison.
-      if (qx > -1.0 && qx < (double)v.xsize && qy > -1.0 && qy < (double)v.ysize) {
-        const int gx = (int)qx, gy = (int)qy;
-        if (gx >= 0 && gx < v.xsize && gy >= 0 && gy < v.ysize) {
-          landed = true;
-          if (!MEAN) {
-            atomicMax(&acc[(size_t)gy * v.xsize + gx], dsm_key(w[2]));
-          } else {
-            const unsigned long long q = (unsigned long long)llrint(w[2] * GEO_FIX);   // two's complement: the sum wraps like int64
-            for (int dy = -v.radius; dy <= v.radius; ++dy) {
-              const int cy = gy + dy;
-              if (cy < 0 || cy >= v.ysize) continue;
-              for (int dx = -v.radius; dx <= v.radius; ++dx) {
-                const int cx = gx + dx;
-                if (cx < 0 || cx >= v.xsize) continue;
-                const size_t cell = (size_t)cy * v.xsize + cx;
-                atomicAdd(&acc[cell], q);
-                atomicAdd(&cnt[cell], 1u);
-              }
+      int gx, gy;
+      if (geo_cell(w[0], w[1], v.xoff, v.yoff_top, v.res, v.xsize, v.ysize, &gx, &gy)) {   // geo_unproject.h: shared with ortho.hip
+        landed = true;
+        if (!MEAN) {
+          atomicMax(&acc[(size_t)gy * v.xsize + gx], dsm_key(w[2]));
+        } else {
+          const unsigned long long q = (unsigned long long)llrint(w[2] * GEO_FIX);   // two's complement: the sum wraps like int64
+          for (int dy = -v.radius; dy <= v.radius; ++dy) {
+            const int cy = gy + dy;
+            if (cy < 0 || cy >= v.ysize) continue;
+            for (int dx = -v.radius; dx <= v.radius; ++dx) {
+              const int cx = gx + dx;
+              if (cx < 0 || cx >= v.xsize) continue;
+              const size_t cell = (size_t)cy * v.xsize + cx;
+              atomicAdd(&acc[cell], q);
+              atomicAdd(&cnt[cell], 1u);
             }
           }
         }

@@ -143,6 +143,14 @@ class SfgsPointCloudViewArgs(C.Structure):
                 ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double)]
 
 
+class SfgsOrthoViewArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("mask", C.c_void_p),
+                ("M", C.c_double * 9), ("c", C.c_double * 3), ("origin", C.c_double * 3), ("cx_pix", C.c_double),
+                ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double), ("xoff", C.c_double),
+                ("yoff_top", C.c_double), ("resolution", C.c_double), ("xsize", C.c_int32), ("ysize", C.c_int32),
+                ("image", C.c_void_p), ("tag", C.c_int32)]
+
+
 class SfgsBlendStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("N", C.c_int32), ("weight_sum_q32", C.c_void_p), ("hits", C.c_void_p),
                 ("weight_max", C.c_void_p)]
@@ -215,6 +223,8 @@ SYMBOLS = {
     "sfgs_pointcloud_scratch_bytes": (_SZ, [_I32, _I32]),
     "sfgs_pointcloud_append": (C.c_int, [C.POINTER(SfgsPointCloudViewArgs), _V, _V, _I64, _V, _V, _SZ, _V]),
     "sfgs_pointcloud_bounds": (C.c_int, [_V, _V, _I64, _V, _V, _SZ, _V]),
+    "sfgs_ortho_accumulate": (C.c_int, [C.POINTER(SfgsOrthoViewArgs), _V, _V, _V]),
+    "sfgs_ortho_resolve": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V, _V, _V, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

@@ -267,17 +267,30 @@ def register_simple(pred, gt):
 
 
 def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mode="max", irange=5, radius=1, view_masks=None,
-                 cloud=None):
+                 cloud=None, ortho=None, images=None):
     """The whole chain with ONE host read: scatter every depth map into a DSM, blank the cells keep_mask excludes, register
     the DSM on gt_dsm (scaling off, as the reference calls dsmr), compare -> dict of Python numbers: mae, rmse, valid_pixels,
     completeness, dx_offset, dy_offset, dz_offset, total_points. gt_dsm: [grid.ysize, grid.xsize] on the GPU.
     cloud: a sfgs.pointcloud.PointCloud that every view is appended to as well (same pixels, same order, no host read), for
-    the script's merged PLY and its bounds; the report does not depend on it."""
+    the script's merged PLY and its bounds; the report does not depend on it.
+    ortho: a sfgs.ortho.OrthoAccumulator that view k is scattered into as well, with tag k + 1 and images[k] (float32 [3,H,W],
+    one per view, needed exactly then) as its colours; the report does not depend on it either."""
     depths, cameras = list(depths), list(cameras)
     if cloud is not None:
         from .pointcloud import PointCloud
         if not isinstance(cloud, PointCloud):
             raise ValueError("cloud must be a sfgs.pointcloud.PointCloud or None")
+    if ortho is not None:
+        from .ortho import OrthoAccumulator
+        if not isinstance(ortho, OrthoAccumulator):
+            raise ValueError("ortho must be a sfgs.ortho.OrthoAccumulator or None")
+        if images is None:
+            raise ValueError("ortho needs images: one float32 [3,H,W] per view")
+        images = list(images)
+        if len(images) != len(depths):
+            raise ValueError(f"{len(images)} images for {len(depths)} depth maps")
+    elif images is not None:
+        raise ValueError("images are used only with ortho")
     if len(depths) != len(cameras) or not depths:
         raise ValueError(f"{len(depths)} depth maps for {len(cameras)} cameras")
     if view_masks is not None and len(view_masks) != len(depths):
@@ -291,6 +304,8 @@ def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mod
         acc.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])
         if cloud is not None:
             cloud.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])
+        if ortho is not None:
+            ortho.add_view(depth, images[k], cam, origin=origin, mask=None if view_masks is None else view_masks[k], tag=k + 1)
     pred = acc.result()
     if keep_mask is not None:                             # evaluate_gs_geometry.py:455-469: water cells are NaN before dsmr
         keep = keep_mask.reshape(grid.ysize, grid.xsize) != 0
