@@ -71,10 +71,16 @@ tile_order_kernel(int TX8, int TY8, int SX, int SY, const void* __restrict__ key
 }
 
 // ------------------------------------------------------------------------------------------------
-// K5: compositing. Workgroup = 4 independent waves = a 2x2 block of 8x8 tiles; lane l of
-// a wave owns pixel (l & 7, l >> 3) of its tile. Records of 64 list entries at a time are gathered
+// K5: compositing. Workgroup = 4 independent waves = a 2x2 block of 8x8 tiles; DPP row q = lane >> 4 of
+// a wave owns the 4x4 quadrant q of its tile (x = 4 (q & 1) + (lane & 3), y = 4 (q >> 1) + ((lane >> 2) & 3)).
+// Records of 64 list entries at a time are gathered
 // (48 B each) into a wave-private LDS stage and consumed with uniform-address (broadcast) reads.
 // No barriers: a wave only ever reads what it wrote itself.
+// Each quadrant walks its own compact list of the batch's entries: those whose alpha >= 1/255 bounding box (mx +- ex,
+// my +- ey) reaches the quadrant in x AND y. (Round 20; before, the rows owned 8x2 strips tested on y alone. Work model,
+// tools/workmodel, headline: list steps per entry 0.728 -> 0.674 in TRAIN's 32-entry halves, 0.707 -> 0.650 in 64-entry
+// batches, i.e. -7.4 / -8.2 %; measured -4.2 % (TRAIN, 0.212 -> 0.203 ms) and -5.5 % (render, 0.190 -> 0.180 ms), bit-identical
+// outputs; 58 -> 60 and 54 -> 56 VGPRs, no scratch. profiles/r20_fwd_quadrant_lists_ab.txt)
 // TRAIN (a backward will follow): every pixel also records WHICH entries it blended, one bit per entry, and the
 // wave stores one 8-byte word per pixel and 64-entry batch (image blob, `hitmask`): the backward then walks each
 // pixel's own blended entries instead of re-testing every (pixel, entry) pair of the list (raster_bwd.hip).
@@ -103,7 +109,12 @@ composite_fwd_kernel(KFrame kf, int TX8, int TY8, int SX, int SY, const uint2* _
   const int lane = threadIdx.x & 63;
   if (tx >= TX8 || ty >= TY8 || ty < kf.band0 || ty >= kf.band1) return;
   const int W = kf.W, H = kf.H;
-  const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+  // lane -> pixel: DPP row q = lane >> 4 owns the 4x4 QUADRANT q of the tile (left / right = q & 1, top / bottom = q >> 1),
+  // its 16 lanes the quadrant's pixels row by row. slot = the pixel's position in image order inside the tile, 8 y + x:
+  // where the backward (lane = 8 y + x) expects this pixel's hit-mask word.
+  const int qx = 4 * ((lane >> 4) & 1), qy = 4 * (lane >> 5);
+  const int slot = 8 * (qy + ((lane >> 2) & 3)) + qx + (lane & 3);
+  const int px = tx * 8 + (slot & 7), py = ty * 8 + (slot >> 3);
   const bool inside = px < W && py < H;
   const size_t pix = (size_t)py * W + px;
   const int t = ty * TX8 + tx;
@@ -129,7 +140,7 @@ composite_fwd_kernel(KFrame kf, int TX8, int TY8, int SX, int SY, const uint2* _
     if (__ballot(ps.T > 0.f) == 0ull) break;  // every pixel of the tile is saturated
     const unsigned cnt = min(64u, e - b);
     st[lane * 3] = n0; st[lane * 3 + 1] = n1; st[lane * 3 + 2] = n2;
-    const float stage_my = n0.y, stage_ey = n2.w;
+    const float stage_mx = n0.x, stage_my = n0.y, stage_ex = n2.z, stage_ey = n2.w;
     if (b + 64 + lane < e) {  // prefetch: records of the next batch, ids of the one after
       n0 = rec[REC_F4 * (size_t)id_next]; n1 = rec[REC_F4 * (size_t)id_next + 1]; n2 = rec[REC_F4 * (size_t)id_next + 2];
     }
@@ -137,21 +148,29 @@ composite_fwd_kernel(KFrame kf, int TX8, int TY8, int SX, int SY, const uint2* _
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     const unsigned k0 = b - s;
-    // Strip skipping. Only ~25 % of the (pixel, splat) pairs of a tile list hit (splats of a few pixels on an 8x8
-    // tile), and a wave cannot skip per lane -- but it can per strip: lanes 16r..16r+15 (one DPP row) own pixel rows
-    // 2r, 2r+1, and an entry whose alpha >= 1/255 region (y-extent my +- ey, margins included) misses those two rows
-    // cannot be accepted by any of their pixels. Each strip therefore walks its own compact list of the batch entries
-    // that can touch it (~65 % of them); the four strips advance in lockstep and the wave leaves the batch when the
-    // longest list is exhausted. Exact: the skipped pairs are pairs the per-pixel test would have rejected.
-    // (Eight single-row lists need fewer steps but twice the list set-up: same time.)
-    const float my = stage_my, ey = stage_ey;   // this lane's STAGED entry (entry index = lane)
-    const float ylo = (float)(ty * 8) - bound, yhi = (float)(ty * 8 + 1) + bound;
+    // Quadrant skipping. Only ~25 % of the (pixel, splat) pairs of a tile list hit (splats of a few pixels on an 8x8
+    // tile), and a wave cannot skip per lane -- but it can per DPP row: lanes 16q..16q+15 own the 4x4 quadrant q, and an
+    // entry whose alpha >= 1/255 region (bounding box mx +- ex, my +- ey: fill_extents, margins included) misses the
+    // quadrant's pixels in x or in y cannot be accepted by any of them. Each quadrant therefore walks its own compact list
+    // of the batch entries that can touch it; the four quadrants advance in lockstep and the wave leaves the batch when the
+    // longest list is exhausted. Exact: the skipped pairs are pairs the per-pixel test would have rejected. The negated
+    // comparisons keep an entry with a NaN or infinite extent (NaN opacity: fill_extents) in every list.
+    // (Until round 20 the rows owned 8x2 strips tested on y alone -- x adds nothing to a strip as wide as the tile: 0.728
+    // list steps per entry on the headline against 0.674 for quadrants, tools/workmodel; same four ballots per batch.
+    // Eight single-row lists needed fewer steps than the strips but twice the list set-up: same time.)
+    const float mx = stage_mx, my = stage_my, ex = stage_ex, ey = stage_ey;   // this lane's STAGED entry (entry index = lane)
+    const float xlo = (float)(tx * 8) - bound, xhi = (float)(tx * 8 + 3) + bound;
+    const float ylo = (float)(ty * 8) - bound, yhi = (float)(ty * 8 + 3) + bound;
     const bool live = (unsigned)lane < cnt;
-    const unsigned long long b0 = __ballot(live && !(my + ey < ylo) && !(my - ey > yhi));
-    const unsigned long long b1 = __ballot(live && !(my + ey < ylo + 2.f) && !(my - ey > yhi + 2.f));
-    const unsigned long long b2 = __ballot(live && !(my + ey < ylo + 4.f) && !(my - ey > yhi + 4.f));
-    const unsigned long long b3 = __ballot(live && !(my + ey < ylo + 6.f) && !(my - ey > yhi + 6.f));
-    // per-row compact entry lists (bytes) in LDS
+    const bool in_l = live && !(mx + ex < xlo) && !(mx - ex > xhi);                 // columns 0..3
+    const bool in_r = live && !(mx + ex < xlo + 4.f) && !(mx - ex > xhi + 4.f);     // columns 4..7
+    const bool in_t = !(my + ey < ylo) && !(my - ey > yhi);                         // rows 0..3
+    const bool in_b = !(my + ey < ylo + 4.f) && !(my - ey > yhi + 4.f);             // rows 4..7
+    const unsigned long long b0 = __ballot(in_l && in_t);
+    const unsigned long long b1 = __ballot(in_r && in_t);
+    const unsigned long long b2 = __ballot(in_l && in_b);
+    const unsigned long long b3 = __ballot(in_r && in_b);
+    // per-quadrant compact entry lists (bytes) in LDS
     unsigned char* Lw = &rowlist[lw][0][0];
     const int row = lane >> 4;
     const unsigned char* Lr = Lw + row * 64;
@@ -224,7 +243,7 @@ composite_fwd_kernel(KFrame kf, int TX8, int TY8, int SX, int SY, const uint2* _
         if (done) break;
       }
       if (mlo | mhi) ps.last = k0 + (mhi ? 63u - (unsigned)__clz(mhi) : 31u - (unsigned)__clz(mlo)) + 1u;
-      hitmask[(size_t)b + lane] = make_uint2(mlo, mhi);   // b is a multiple of 64: one 512-byte store per batch
+      hitmask[(size_t)b + slot] = make_uint2(mlo, mhi);   // b is a multiple of 64: one 512-byte store per batch, word 8 y + x
     }
     __builtin_amdgcn_wave_barrier();
   }

@@ -346,8 +346,9 @@ struct ImageView {
   uint32_t* n_contrib;  // [P] list position (1-based) of the last contributor
   float* final_T;       // [P]
   float* dacc;          // [P] un-normalised accumulated depth
-  uint2* hitmask;       // [slot capacity] word (first slot of the tile + 64 b + lane) = which of the 64 entries of the
-                        //   tile's b-th batch pixel `lane` BLENDED (bit j of .x: entry j, bit j of .y: entry 32 + j)
+  uint2* hitmask;       // [slot capacity] word (first slot of the tile + 64 b + p) = which of the 64 entries of the
+                        //   tile's b-th batch pixel p = 8 y + x of the tile BLENDED (bit j of .x: entry j, bit j of .y: entry
+                        //   32 + j); p is the backward's lane, not the forward's (composite_fwd: lanes own quadrants)
   uint32_t* tile_kmax;  // [T8] list position (1-based) of the tile's LAST contributor = max of n_contrib over its pixels
   uint16_t* tile_dead;  // [T8] min(65535, list entries behind the last contributor)
 };

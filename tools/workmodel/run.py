@@ -52,7 +52,8 @@ def main():
              "dead_entries", "live_entries", "behind", "task_nonzero", "task_total", "D_all", "all16_batches",
              "live16_batches", "f64_bbox", "f64_xy", "f64_exact", "f64_ideal", "f32_bbox", "f32_xy", "f32_exact", "f32_ideal",
              "fwd_steps", "fwd_steps_no_accept", "row_task_nonzero", "row_task_total", "p2_groups_zero", "p2_groups", "sp16_ahead",
-             "walk_waves", "walk_steps_max", "walk_steps_balanced", "walk_tiles", "walk_rows_max", "walk_waves_over32", "walk_steps_hybrid"]
+             "walk_waves", "walk_steps_max", "walk_steps_balanced", "walk_tiles", "walk_rows_max", "walk_waves_over32", "walk_steps_hybrid",
+             "fq64_xy", "fq64_exact", "fq64_ideal", "fq32_xy", "fq32_exact", "fq32_ideal"]
     v = dict(zip(names, out[:nv]))
     T = v["n_tiles"]
     print(f"tiles {T:.0f}  mean list {v['sumL']/T:.1f}  mean kmax {v['sumK']/T:.1f}  D_all {v['D_all']:.0f}")
@@ -64,6 +65,10 @@ def main():
     print(f"phase-2 (entry,row-pair) tasks non-zero: {v['task_nonzero']/v['task_total']:.3f}")
     for k in ("f64_bbox", "f64_xy", "f64_exact", "f64_ideal", "f32_bbox", "f32_xy", "f32_exact", "f32_ideal"):
         print(f"  forward strip-list steps {k:10s}: {v[k]/v['sumK']:.3f} of kmax")
+    # the forward's lists as 4x4 quadrants (one per DPP row; shipped since round 20: fq*_xy) instead of 8x2 strips
+    for k in ("fq64_xy", "fq64_exact", "fq64_ideal", "fq32_xy", "fq32_exact", "fq32_ideal"):
+        print(f"  forward quadrant-list steps {k:10s}: {v[k]/v['sumK']:.3f} of kmax")
+    print(f"  quadrants (x and y extent) over strips (y extent): B = 32 {v['fq32_xy']/v['f32_bbox']:.4f}, B = 64 {v['fq64_xy']/v['f64_bbox']:.4f}")
     print(f"16-batches after dropping dead entries: {v['live16_batches']/v['all16_batches']:.3f}")
     # round 5: what the "skip work nobody needs" ideas could skip
     print(f"forward (TRAIN, 32-entry halves): strip-list steps in which NO lane of the wave blends its entry: "

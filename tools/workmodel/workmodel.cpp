@@ -81,6 +81,7 @@ int wm_run(const WmFrame* hf, int32_t N, const float* means, const float* scales
   double hist_hits[65] = {0};
   double live16_batches = 0, all16_batches = 0;           // batches (of 16) after dropping dead entries
   double fstrip64[4] = {0, 0, 0, 0}, fstrip32[4] = {0, 0, 0, 0};   // forward strip-list steps (see below)
+  double fquad64[4] = {0, 0, 0, 0}, fquad32[4] = {0, 0, 0, 0};     // forward quadrant-list steps (see below)
   // round 5:
   double fwd_steps = 0, fwd_steps_no_accept = 0;   // strip-list steps of the forward (32-entry halves, bbox lists) / those in
                                                    // which NO lane of the wave blends (a wave-uniform early-out could skip the blend)
@@ -217,6 +218,36 @@ int wm_run(const WmFrame* hf, int32_t N, const float* means, const float* scales
         return steps;
       };
       for (int m = 0; m < 4; ++m) { fstrip64[m] += fwd(64, m); fstrip32[m] += fwd(32, m); }
+      // FORWARD quadrant lists: the same four lists per batch, one per DPP row, but row q owns the 4x4 quadrant q of the
+      // tile (x = 4 (q & 1) .., y = 4 (q >> 1) ..) instead of two pixel rows. `xy` = x- AND y-extent reach the quadrant
+      // (a y-only test is the two-list 8x4 case: no quadrant test), `exact` = the ellipse reaches the quadrant's
+      // rectangle, `ideal` = at least one pixel of the quadrant blended it. Indices as fstrip: [1] xy, [2] exact, [3] ideal.
+      auto fwdq = [&](int B, int mode) {
+        double steps = 0;
+        const float X0 = (float)((tx0 + tx) * 8), Y0 = (float)((ty0 + ty) * 8);
+        for (int b0 = 0; b0 < kmax; b0 += B) {
+          int cnt[4] = {0, 0, 0, 0};
+          for (int k = b0; k < std::min(kmax, b0 + B); ++k) {
+            const SplatRec& r = recs[(unsigned)(l[k] & 0xffffffffull)];
+            for (int q = 0; q < 4; ++q) {
+              const float x0 = X0 + 4.f * (q & 1), x1 = x0 + 3.f, y0 = Y0 + 4.f * (q >> 1), y1 = y0 + 3.f;
+              bool in;
+              if (mode == 3) {
+                unsigned long long qm = 0;
+                for (int y = 0; y < 4; ++y) qm |= 0xfull << (((q >> 1) * 4 + y) * 8 + (q & 1) * 4);
+                in = (emask[k] & qm) != 0;
+              } else {
+                in = !(r.my + r.ey < y0) && !(r.my - r.ey > y1) && !(r.mx + r.ex < x0) && !(r.mx - r.ex > x1);
+                if (mode == 2) in = in && reach(r, x0, x1, y0, y1);
+              }
+              if (in) ++cnt[q];
+            }
+          }
+          steps += *std::max_element(cnt, cnt + 4);
+        }
+        return steps;
+      };
+      for (int m = 1; m < 4; ++m) { fquad64[m] += fwdq(64, m); fquad32[m] += fwdq(32, m); }
       {   // the forward as shipped (TRAIN: halves of 32 entries, y-extent strip lists in lockstep): in how many of its steps does
           // no lane of the wave accept its entry? (each strip is on ITS i-th entry of the half)
         const float Y0 = (float)((ty0 + ty) * 8);
@@ -244,7 +275,8 @@ int wm_run(const WmFrame* hf, int32_t N, const float* means, const float* scales
                    live_entries, behind, task_nonzero, task_total, (double)D_all, all16_batches, live16_batches,
                    fstrip64[0], fstrip64[1], fstrip64[2], fstrip64[3], fstrip32[0], fstrip32[1], fstrip32[2], fstrip32[3],
                    fwd_steps, fwd_steps_no_accept, row_task_nonzero, row_task_total, p2_groups_zero, p2_groups, sp16_ahead,
-                   walk_waves, walk_steps_max, walk_steps_balanced, walk_tiles, walk_rows_max, walk_waves_over32, walk_steps_hybrid};
+                   walk_waves, walk_steps_max, walk_steps_balanced, walk_tiles, walk_rows_max, walk_waves_over32, walk_steps_hybrid,
+                   fquad64[1], fquad64[2], fquad64[3], fquad32[1], fquad32[2], fquad32[3]};
   int nv = (int)(sizeof(vals) / sizeof(vals[0]));
   for (int i = 0; i < nv && i < n_out; ++i) out[i] = vals[i];
   for (int i = 0; i < 65 && nv + i < n_out; ++i) out[nv + i] = hist_hits[i];
