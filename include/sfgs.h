@@ -22,6 +22,7 @@
  *   sfgs_dsmr_*        dsmr.compute_shift (recursive_ncc, mean_std), dsmr.apply_shift_   dsmr.py:16-149
  *   sfgs_pointcloud_*  depth_to_point_cloud per view, np.vstack, the cloud's bounds   evaluate_gs_geometry.py:132-215,776,787-790
  *   sfgs_ortho_*       (no counterpart: the script renders RGB per camera next to the depth, writes it to a PNG and keeps no georeferenced colour)   evaluate_gs_geometry.py:736-765
+ *   sfgs_consistency_* (no counterpart: the script unprojects every rendered depth pixel it gets, evaluate_gs_geometry.py:767-776, and has no filter between the views)
  *   sfgs_raster_blend_stats, sfgs_blend_stats_views  (no counterpart: the reference's only pruning tool is GaussianModel.prune_by_radius, scene/gaussian_model.py:752, by distance)
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
@@ -770,6 +771,48 @@ typedef struct SfgsOrthoViewArgs {
 int sfgs_ortho_accumulate(const SfgsOrthoViewArgs* args, void* acc, unsigned long long* num_points, void* stream);
 int sfgs_ortho_resolve(int32_t xsize, int32_t ysize, int32_t fill, const void* acc, unsigned char* rgb, float* height,
                        unsigned char* source, unsigned char* state, unsigned long long* coverage, void* stream);
+
+/* ---- Multi-view depth consistency masks (added under ABI 28: new symbols only; csrc/consistency.hip; Python: sfgs.consistency):
+ * the per-view pixel mask the three geometry products above take. A rendered depth is an alpha-blended expectation: at a roof
+ * edge it mixes roof and ground and unprojects to a point in mid-air. A pixel of view i is kept when at least min_views OTHER
+ * views see the same surface there. float64 throughout, nothing contracted, products, sums and quotients in the order written.
+ *   project(k, w):  q_n = w_n - c_k[n];  cam_a = (q_0 M_k[3a] + q_1 M_k[3a+1]) + q_2 M_k[3a+2];  z = cam_2;
+ *                   u = cam_0 focal_x / z + cx_pix;  v = cam_1 focal_y / z + cy_pix
+ *   unproject(k, row, col, d): stage 1's of the geometry evaluation above (the same device function), origin = 0.
+ *   A pixel is USED by stage 1's rule: depth > 0, finite, mask byte (if any) non-zero.
+ * For pixel (r, c) of the reference view i: not used -> count = keep = 0. Otherwise w = unproject(i, r, c, d) and every
+ * j != i, ascending, is accepted if all of these hold in turn:
+ *   (u, v, z) = project(j, w), z > 0;
+ *   fu = floor(u + 0.5), fv = floor(v + 0.5), 0 <= fu < W_j, 0 <= fv < H_j (tested on the doubles; NaN fails);
+ *   pixel (fv, fu) of j is used, with depth d_j;
+ *   |(double)d_j - z| <= rel_tol * z;
+ *   w' = unproject(j, fv, fu, d_j), (u', v', z') = project(i, w'), z' > 0 and (u' - c)^2 + (v' - r)^2 <= px_tol2.
+ * count[r][c] = the accepted sources (<= 255), keep[r][c] = count >= min_views; one byte each.
+ * The views live in a DEVICE table of V records, written once per set by the caller (sfgs_consistency_table_check vets the
+ * host copy before it is uploaded: V, sizes, NULL depth, zero focal lengths); sfgs_consistency_check is ONE launch for one
+ * reference view, a thread per pixel, no atomics, no host read, no synchronise: two runs give the same bytes.
+ * args->H, W size the launch and the two outputs; they must be record `ref`'s (the kernel compares and writes nothing otherwise).
+ * Refusals are SFGS_E_ARG, made before any GPU work. No profiler ids. */
+typedef struct SfgsConsistencyView {
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel, or NULL */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  double M[9];                   /* camera-to-world rotation, row-major: world = cam @ M + c (orthonormal) */
+  double c[3];                   /* camera centre */
+  double cx_pix, cy_pix, focal_x, focal_y;
+} SfgsConsistencyView;
+typedef struct SfgsConsistencyArgs {
+  uint32_t struct_size;          /* = sizeof(SfgsConsistencyArgs) */
+  int32_t V;                     /* records in the table, 2 ... 256 */
+  int32_t ref;                   /* the reference view, 0 ... V - 1 */
+  int32_t H, W;                  /* of the reference view */
+  int32_t min_views;             /* >= 1 */
+  const void* table;             /* device, SfgsConsistencyView [V], 8-byte aligned */
+  double rel_tol;                /* finite, > 0 */
+  double px_tol2;                /* the pixel tolerance SQUARED, > 0; +inf: no bound on the round trip (z' > 0 still holds) */
+} SfgsConsistencyArgs;
+int sfgs_consistency_table_check(const SfgsConsistencyView* host_views, int32_t V);
+int sfgs_consistency_check(const SfgsConsistencyArgs* args, unsigned char* count, unsigned char* keep, void* stream);
 
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the

@@ -35,6 +35,23 @@ __device__ __forceinline__ void geo_unproject(const GeoCamera& v, int row, int c
   }
 }
 
+// World point -> (u, v, z) in view v: pixel coordinates (columns, rows) and the depth along the camera's forward axis, the
+// inverse of geo_unproject for an orthonormal M (cam = (w - c) @ M^T). v.origin is not used: consistency.hip, the one caller,
+// keeps it at zero. z is not tested here; with z == 0 u and v are infinite or NaN, and the caller rejects z <= 0 first.
+// tests/consistency_np.project states the same sequence in numpy.
+__device__ __forceinline__ void geo_project(const GeoCamera& v, const double (&w)[3], double* u, double* vv, double* z) {
+  const double q0 = w[0] - v.c[0], q1 = w[1] - v.c[1], q2 = w[2] - v.c[2];
+  double cam[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double t = q0 * v.M[3 * a] + q1 * v.M[3 * a + 1];
+    cam[a] = t + q2 * v.M[3 * a + 2];
+  }
+  *z = cam[2];
+  *u = cam[0] * v.focal_x / cam[2] + v.cx_pix;
+  *vv = cam[1] * v.focal_y / cam[2] + v.cy_pix;
+}
+
 // The grid cell of a world point: geometry.hip's height grid and ortho.hip's colour grid are held to each other cell for cell.
 // (int) truncates toward zero: (-1, 0) lands in cell 0, as numpy's astype(int) does. NaN fails every comparison. The open
 // interval is tested on the float64 first (a value beyond int's range is never converted), the integer range after it.

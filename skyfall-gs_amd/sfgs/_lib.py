@@ -151,6 +151,17 @@ class SfgsOrthoViewArgs(C.Structure):
                 ("image", C.c_void_p), ("tag", C.c_int32)]
 
 
+class SfgsConsistencyView(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("mask", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_double * 9),
+                ("c", C.c_double * 3), ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double),
+                ("focal_y", C.c_double)]
+
+
+class SfgsConsistencyArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("ref", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("min_views", C.c_int32), ("table", C.c_void_p), ("rel_tol", C.c_double), ("px_tol2", C.c_double)]
+
+
 class SfgsBlendStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("N", C.c_int32), ("weight_sum_q32", C.c_void_p), ("hits", C.c_void_p),
                 ("weight_max", C.c_void_p)]
@@ -225,6 +236,8 @@ SYMBOLS = {
     "sfgs_pointcloud_bounds": (C.c_int, [_V, _V, _I64, _V, _V, _SZ, _V]),
     "sfgs_ortho_accumulate": (C.c_int, [C.POINTER(SfgsOrthoViewArgs), _V, _V, _V]),
     "sfgs_ortho_resolve": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V, _V, _V, _V]),
+    "sfgs_consistency_table_check": (C.c_int, [C.POINTER(SfgsConsistencyView), _I32]),
+    "sfgs_consistency_check": (C.c_int, [C.POINTER(SfgsConsistencyArgs), _V, _V, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

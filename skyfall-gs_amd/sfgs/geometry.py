@@ -267,15 +267,21 @@ def register_simple(pred, gt):
 
 
 def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mode="max", irange=5, radius=1, view_masks=None,
-                 cloud=None, ortho=None, images=None):
+                 cloud=None, ortho=None, images=None, consistency=None):
     """The whole chain with ONE host read: scatter every depth map into a DSM, blank the cells keep_mask excludes, register
     the DSM on gt_dsm (scaling off, as the reference calls dsmr), compare -> dict of Python numbers: mae, rmse, valid_pixels,
     completeness, dx_offset, dy_offset, dz_offset, total_points. gt_dsm: [grid.ysize, grid.xsize] on the GPU.
     cloud: a sfgs.pointcloud.PointCloud that every view is appended to as well (same pixels, same order, no host read), for
     the script's merged PLY and its bounds; the report does not depend on it.
     ortho: a sfgs.ortho.OrthoAccumulator that view k is scattered into as well, with tag k + 1 and images[k] (float32 [3,H,W],
-    one per view, needed exactly then) as its colours; the report does not depend on it either."""
+    one per view, needed exactly then) as its colours; the report does not depend on it either.
+    consistency: None, or {"rel_tol": ..., "px_tol": ..., "min_views": ...}: the multi-view consistency masks of
+    sfgs.consistency are computed first, from depths, cameras and view_masks, and take the place of view_masks for the DSM, the
+    cloud and the orthophoto -- evaluate_dsm(..., view_masks=ViewSet(depths, cameras, view_masks).masks(**consistency))."""
     depths, cameras = list(depths), list(cameras)
+    if consistency is not None:
+        from .consistency import ViewSet, check_options
+        consistency = check_options(consistency)
     if cloud is not None:
         from .pointcloud import PointCloud
         if not isinstance(cloud, PointCloud):
@@ -299,6 +305,8 @@ def evaluate_dsm(depths, cameras, grid, gt_dsm, origin=None, keep_mask=None, mod
         raise ValueError(f"gt_dsm {tuple(gt_dsm.shape)} is not the grid's {(grid.ysize, grid.xsize)}")
     _call.check_pixel_mask(keep_mask, grid.ysize, grid.xsize, "keep_mask")
     _call.check_gpu(gt_dsm=gt_dsm)
+    if consistency is not None:
+        view_masks = ViewSet(depths, cameras, view_masks).masks(**consistency)
     acc = DsmAccumulator(grid, mode=mode, radius=radius, device=gt_dsm.device)
     for k, (depth, cam) in enumerate(zip(depths, cameras)):
         acc.add_view(depth, cam, origin=origin, mask=None if view_masks is None else view_masks[k])
