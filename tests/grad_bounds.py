@@ -35,6 +35,7 @@ import torch
 from oracle import oracle as orc
 from sfgs.synth import scene, upstream_grads
 
+import camera_cases
 import raster_chain_np
 
 DELTA = 2.0 ** -16
@@ -61,6 +62,11 @@ CASES = {
     "big_splats_alpha": dict(_BIG_SPLATS, alpha=True),
     "big_splats_alpha_raw": dict(_BIG_SPLATS, alpha=True, depth_mode=1),
 }
+# general cameras (tests/camera_cases.py builds them: pose, off-centre principal point, splats beyond the Jacobian's guard
+# band, depths down to the near cull); clamped_jacobian masks 1.07 % of its pixels at seed 3 and takes seed 4
+for _name in ("clamped_jacobian", "near_plane", "pose_offcentre_sh3"):
+    CASES[_name] = dict(camera=_name, n=camera_cases.CASES[_name]["n"], W=camera_cases.CASES[_name]["W"],
+                        H=camera_cases.CASES[_name]["H"])
 
 # case -> tensor -> (accf, jit, chain64, K): the measured maxima, in units, of the float32-sum build, the exp-jitter build
 # and the float64 chain against the oracle (rounded up to three digits); K = 4 x the largest, rounded up to a power of two.
@@ -153,6 +159,32 @@ K_TABLE = {
         "opacities": (0.0165, 0.329, 0.0166, 2),
         "colors_precomp": (0.0379, 0.758, 0.00741, 4),
     },
+    # general pose: the world coordinates (|p| ~ 14) cancel down to view-space ones in every product with the view and
+    # projection matrices, so the unit of means3D is large next to its value and the readings, in units, are small
+    "clamped_jacobian": {
+        "means3D": (0.000199, 0.00261, 0.000463, 0.015625),
+        "means2D": (0.0275, 0.0372, 0.00452, 0.25),
+        "scales": (0.000261, 0.00161, 0.000192, 0.0078125),
+        "rotations": (0.000338, 0.000386, 0.000142, 0.001953125),
+        "opacities": (0.0179, 0.0354, 0.00117, 0.25),
+        "colors_precomp": (0.0419, 0.804, 0.0268, 4),
+    },
+    "near_plane": {
+        "means3D": (0.000139, 0.0026, 0.000408, 0.015625),
+        "means2D": (0.0612, 0.833, 0.0137, 4),
+        "scales": (0.0031, 0.0677, 0.00872, 0.5),
+        "rotations": (0.00242, 0.0369, 0.00448, 0.25),
+        "opacities": (0.0584, 1.78, 0.0204, 8),
+        "colors_precomp": (0.135, 2.75, 0.0218, 16),
+    },
+    "pose_offcentre_sh3": {
+        "means3D": (0.000391, 0.00313, 0.000353, 0.015625),
+        "means2D": (0.0912, 0.361, 0.0162, 2),
+        "scales": (0.00733, 0.0586, 0.0114, 0.25),
+        "rotations": (0.00441, 0.0233, 0.00361, 0.125),
+        "opacities": (0.0417, 0.317, 0.0315, 2),
+        "shs": (0.662, 1.87, 0.673, 8),
+    },
 }
 
 
@@ -174,7 +206,10 @@ def _round_up(v):
 
 def make_case(name):
     c = CASES[name]
-    frame, g = scene(c["n"], c["W"], c["H"], seed=c.get("seed", 7), **c["kw"])
+    if "camera" in c:
+        frame, g, _ = camera_cases.case(c["camera"])
+    else:
+        frame, g = scene(c["n"], c["W"], c["H"], seed=c.get("seed", 7), **c["kw"])
     frame["depth_mode"] = int(c.get("depth_mode", 0))
     return frame, g
 

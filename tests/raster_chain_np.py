@@ -86,10 +86,13 @@ def _f32(x):
     return np.asarray(x, np.float32)
 
 
-def chain(frame, means3D, scales, rotations, opacities, shs, state, visible, sums, mags=None, magnitude=False):
+def chain(frame, means3D, scales, rotations, opacities, shs, state, visible, sums, mags=None, magnitude=False,
+          clamp_mul=True):
     """frame: the dict of sfgs.camera.make_frame. means3D .. shs: the float32 inputs (shs [N,M,3] or None).
     state: OracleRender.chain_state(). visible: radii > 0. sums [N,12]: the per-Gaussian 2D sums in Acc2D / Grad2D order
     (gmx, gmy, absx, absy, gA, gB, gC, gop, gr, gg, gb, gdepth). mags [N,12]: their magnitudes (default |sums|).
+    clamp_mul=False: the WRONG chain that lets a clamped Jacobian coordinate pass its gradient on (x_mul = y_mul = 1); the
+    tests use it to show that they would notice that defect (tests/test_gpu_camera_model.py), nothing else may.
     Returns a dict of float64 arrays shaped like the oracle's gradients; invisible Gaussians get zeros."""
     N = int(np.asarray(means3D).shape[0])
     idx = np.nonzero(np.asarray(visible))[0]
@@ -175,6 +178,8 @@ def chain(frame, means3D, scales, rotations, opacities, shs, state, visible, sum
     gJ11 = gT1[0] * Vm[1] + gT1[1] * Vm[5] + gT1[2] * Vm[9]
     gJ12 = gT1[0] * Vm[2] + gT1[1] * Vm[6] + gT1[2] * Vm[10]
     x_mul, y_mul = (~out_x).astype(np.float64), (~out_y).astype(np.float64)
+    if not clamp_mul:
+        x_mul, y_mul = np.ones_like(x_mul), np.ones_like(y_mul)
     gtx = x_mul * (-fx * tz2) * gJ02
     gty = y_mul * (-fy * tz2) * gJ12
     gtz = -fx * tz2 * gJ00 - fy * tz2 * gJ11 + (2.0 * fx * ux) * tz3 * gJ02 + (2.0 * fy * uy) * tz3 * gJ12

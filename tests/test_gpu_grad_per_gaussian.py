@@ -159,6 +159,44 @@ def test_lists_800_deep_lists():
     check("lists_800", ref, out)
 
 
+def test_clamped_jacobian_rows_beyond_the_guard_band():
+    """general pose (tests/camera_cases.py); visible splats beyond 1.3 tanfov: ux / uy clamped, x_mul / y_mul = 0"""
+    import camera_cases as cc
+    ref = gb.reference("clamped_jacobian")
+    frame, _, reach = cc.case("clamped_jacobian")
+    cx, cy = cc.clamped(frame, reach)
+    w = gb.has_gradient("clamped_jacobian")
+    print("clamped_jacobian: with a gradient and clamped in x", int((cx & w).sum()), "in y", int((cy & w).sum()), "in both",
+          int((cx & cy & w).sum()))
+    assert (cx & w).sum() >= 50 and (cy & w).sum() >= 50 and (cx & cy & w).sum() >= 5
+    check("clamped_jacobian", ref, run_hip(ref), whole_tensor=True)
+
+
+def test_near_plane_depths_down_to_the_cull():
+    """general pose; 1 / tz^3 of up to 125 in the backward, and Gaussians on the other side of tz > 0.2 in the same frame"""
+    import camera_cases as cc
+    ref = gb.reference("near_plane")
+    near, culled = cc.near_band(cc.case("near_plane")[2])
+    w = gb.has_gradient("near_plane")
+    print("near_plane: with a gradient and 0.2 < tz < 0.3", int((near & w).sum()), "culled with 0 < tz <= 0.2", int(culled.sum()))
+    assert (near & w).sum() >= 100 and culled.sum() >= 100 and (ref["R"].radii[culled] == 0).all()
+    check("near_plane", ref, run_hip(ref), whole_tensor=True)
+
+
+def test_general_pose_offcentre_principal_point_and_band3():
+    """general pose, principal point at (0.12, -0.08) NDC, SH degree 3 seen from campos = (12, -7, 3)"""
+    ref = gb.reference("pose_offcentre_sh3")
+    f = ref["frame"]
+    assert f["sh_degree"] == 3 and float(f["campos"].abs().min()) > 1
+    P = f["proj"].numpy()
+    assert abs(P[2, 0]) > 0.05 and abs(P[2, 1]) > 0.05                       # the principal-point terms of mean2D
+    rot = np.abs(f["view"].numpy()[:3, :3]).ravel()
+    assert rot.min() > 0.01 and np.diff(np.sort(rot)).min() > 0.01           # no entry is zero, no two can be swapped
+    assert gb.has_gradient("pose_offcentre_sh3").all()
+    assert np.abs(ref["G"]["shs"][:, 9:]).max() > 0
+    check("pose_offcentre_sh3", ref, run_hip(ref), whole_tensor=True)
+
+
 @pytest.mark.parametrize("case", ["precomp_small_alpha", "precomp_small_alpha_raw", "big_splats_alpha",
                                   "big_splats_alpha_raw"])
 def test_alpha_term_and_raw_depth_mode(case):
