@@ -23,6 +23,7 @@
  *   sfgs_pointcloud_*  depth_to_point_cloud per view, np.vstack, the cloud's bounds   evaluate_gs_geometry.py:132-215,776,787-790
  *   sfgs_ortho_*       (no counterpart: the script renders RGB per camera next to the depth, writes it to a PNG and keeps no georeferenced colour)   evaluate_gs_geometry.py:736-765
  *   sfgs_consistency_* (no counterpart: the script unprojects every rendered depth pixel it gets, evaluate_gs_geometry.py:767-776, and has no filter between the views)
+ *   sfgs_tsdf_*        (no counterpart: the script has no mesh step; its geometry products are the DSM and the merged cloud, evaluate_gs_geometry.py:776-784)
  *   sfgs_raster_blend_stats, sfgs_blend_stats_views  (no counterpart: the reference's only pruning tool is GaussianModel.prune_by_radius, scene/gaussian_model.py:752, by distance)
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
@@ -813,6 +814,65 @@ typedef struct SfgsConsistencyArgs {
 } SfgsConsistencyArgs;
 int sfgs_consistency_table_check(const SfgsConsistencyView* host_views, int32_t V);
 int sfgs_consistency_check(const SfgsConsistencyArgs* args, unsigned char* count, unsigned char* keep, void* stream);
+
+/* ---- TSDF fusion and mesh extraction (added under ABI 28: new symbols only; csrc/tsdf.hip, csrc/tsdf_math.h; Python: sfgs.tsdf):
+ * depth views -> a truncated signed distance volume -> a triangle soup by marching tetrahedra. The volume is axis-aligned in the
+ * cameras' frame: voxel (i, j, k) has its centre at origin + (i + 0.5, j + 0.5, k + 0.5) * voxel_size, formed in float64 as
+ * written; storage is planar float32, x fastest: tsdf [nz][ny][nx], weight [nz][ny][nx], rgb [3][nz][ny][nx] (or NULL).
+ * INTEGRATION, sfgs_tsdf_integrate: ONE launch for V <= 256 views held in a device table (sfgs_tsdf_table_check vets the host copy
+ * first, with with_images = (vol->rgb != NULL): the library cannot read the device copy). A thread owns one voxel, keeps (D, W, rgb) in registers and walks the views in ascending order; float64 on the stored
+ * float32 values, nothing contracted; project() and the USED rule are those of the consistency check above (the same device functions):
+ *   (u, v, z) = project(view, centre); leave unless z > 0;
+ *   fu = floor(u + 0.5), fv = floor(v + 0.5); leave unless 0 <= fu < W and 0 <= fv < H (tested on the doubles; NaN fails);
+ *   leave unless pixel (fv, fu) is used, with depth d;   sdf = (double)d - z; leave if sdf < -trunc;   s = min(1, sdf / trunc);
+ *   D = float32((W D + s) / (W + 1));  with colours, per channel, C = float32((W C + image[ch][fv][fu]) / (W + 1));
+ *   W = float32(min(W + 1, max_weight)).
+ * A voxel is stored only if some view updated it. No atomics, no workgroup waits for another; a voxel's bits depend on the order
+ * of the views alone, so one call with all views, one call per view and any split of the list give the same bytes.
+ * EXTRACTION, sfgs_tsdf_extract, three launches. Cell (x, y, z) spans voxels x..x+1, y..y+1, z..z+1; cells are numbered in the
+ * volume's linear order over (nz-1, ny-1, nx-1); a cell is used only if all eight corner weights are > 0. Corner k has the offsets
+ * (k & 1, (k >> 1) & 1, (k >> 2) & 1). The six tetrahedra are the corner paths (0, 1<<a, (1<<a)|(1<<b), 7) over the permutations
+ * (a, b, c) of (0, 1, 2) in lexicographic order; the local vertices 0..3 of a tetrahedron are its path. A vertex is inside when
+ * its value is < 0 (0 is outside). The point on the edge of local vertices l < m, float32 as written, a = vertex l, b = vertex m:
+ *   t = va / (va - vb);  pos = pa + t * (pb - pa) per axis in voxel-index units;  world = float32(origin) + (pos + 0.5) * float32(voxel_size);
+ *   colour = ca + t * (cb - ca) per channel
+ * (the same bytes from every tetrahedron that shares the edge: the soup welds by byte equality). Triangles of a tetrahedron:
+ *   one inside, vertex i: the edge points (i, j), j ascending;   three inside, outside vertex o: the edge points (i, o), i ascending;
+ *   two inside, i0 < i1, o0 < o1: q0 = (i0, o0), q1 = (i0, o1), q2 = (i1, o1), q3 = (i1, o0): (q0, q1, q2) and (q0, q2, q3);
+ * then the last two vertices are swapped where a 6 x 16 bit table says so, so that (b - a) x (c - a) points toward positive values.
+ * Pass 1 counts the triangles of each workgroup of 256 consecutive cells (0 ... 12 per cell); pass 2, ONE workgroup, scans the
+ * counts 1024 at a time with a carry and leaves the total in *state; pass 3 writes each workgroup's triangles as one run:
+ *   vertices  float32 [capacity][3][3], colors float32 [capacity][3][3] (given exactly when vol->rgb is), ordered by cell, then
+ *             tetrahedron, then triangle. A row at or beyond capacity is not written; *state counts it all the same.
+ *   scratch   sfgs_tsdf_scratch_bytes bytes for the volume's dims, 8-byte aligned.
+ * Refusals are SFGS_E_ARG, made before any GPU work: a NULL pointer, a wrong struct_size, a dimension < 1 or nx ny nz > 2^30,
+ * voxel_size or trunc not finite and > 0, max_weight < 1 or NaN, V outside 1 ... 256, a record with H or W < 1, H W > 2^30, a NULL
+ * depth, a zero focal length, an image pointer that does not go with vol->rgb, a negative capacity, a scratch too small. No profiler ids. */
+typedef struct SfgsTsdfView {
+  const float* depth;            /* device, [H][W] float32 */
+  const unsigned char* mask;     /* device, [H][W] one byte per pixel, or NULL */
+  const float* image;            /* device, [3][H][W] float32, or NULL (a volume without colours) */
+  int32_t H, W;                  /* > 0, H * W <= 2^30 */
+  double M[9];                   /* camera-to-world rotation, row-major: world = cam @ M + c (orthonormal) */
+  double c[3];                   /* camera centre */
+  double cx_pix, cy_pix, focal_x, focal_y;
+} SfgsTsdfView;
+typedef struct SfgsTsdfVolume {
+  uint32_t struct_size;          /* = sizeof(SfgsTsdfVolume) */
+  int32_t nx, ny, nz;            /* > 0, nx * ny * nz <= 2^30 */
+  double origin[3];              /* the corner of voxel (0, 0, 0) */
+  double voxel_size;             /* finite, > 0 */
+  double trunc;                  /* finite, > 0 */
+  double max_weight;             /* >= 1 (+inf: no cap) */
+  float* tsdf;                   /* device, [nz][ny][nx] */
+  float* weight;                 /* device, [nz][ny][nx] */
+  float* rgb;                    /* device, [3][nz][ny][nx], or NULL */
+} SfgsTsdfVolume;
+int sfgs_tsdf_table_check(const SfgsTsdfView* host_views, int32_t V, int32_t with_images);
+int sfgs_tsdf_integrate(const SfgsTsdfVolume* vol, const void* table, int32_t V, void* stream);
+size_t sfgs_tsdf_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);   /* 0: bad arguments (sfgs_last_error) */
+int sfgs_tsdf_extract(const SfgsTsdfVolume* vol, float* vertices, float* colors, int64_t capacity, unsigned long long* state,
+                      void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the

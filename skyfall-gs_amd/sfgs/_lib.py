@@ -157,6 +157,18 @@ class SfgsConsistencyView(C.Structure):
                 ("focal_y", C.c_double)]
 
 
+class SfgsTsdfView(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("mask", C.c_void_p), ("image", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
+                ("M", C.c_double * 9), ("c", C.c_double * 3), ("cx_pix", C.c_double), ("cy_pix", C.c_double),
+                ("focal_x", C.c_double), ("focal_y", C.c_double)]
+
+
+class SfgsTsdfVolume(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_double * 3),
+                ("voxel_size", C.c_double), ("trunc", C.c_double), ("max_weight", C.c_double), ("tsdf", C.c_void_p),
+                ("weight", C.c_void_p), ("rgb", C.c_void_p)]
+
+
 class SfgsConsistencyArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("ref", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("min_views", C.c_int32), ("table", C.c_void_p), ("rel_tol", C.c_double), ("px_tol2", C.c_double)]
@@ -238,6 +250,10 @@ SYMBOLS = {
     "sfgs_ortho_resolve": (C.c_int, [_I32, _I32, _I32, _V, _V, _V, _V, _V, _V, _V]),
     "sfgs_consistency_table_check": (C.c_int, [C.POINTER(SfgsConsistencyView), _I32]),
     "sfgs_consistency_check": (C.c_int, [C.POINTER(SfgsConsistencyArgs), _V, _V, _V]),
+    "sfgs_tsdf_table_check": (C.c_int, [C.POINTER(SfgsTsdfView), _I32, _I32]),
+    "sfgs_tsdf_integrate": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _I32, _V]),
+    "sfgs_tsdf_scratch_bytes": (_SZ, [_I32, _I32, _I32]),
+    "sfgs_tsdf_extract": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _V, _I64, _V, _V, _SZ, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),
