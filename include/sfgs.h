@@ -874,6 +874,61 @@ size_t sfgs_tsdf_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);   /* 0: bad 
 int sfgs_tsdf_extract(const SfgsTsdfVolume* vol, float* vertices, float* colors, int64_t capacity, unsigned long long* state,
                       void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- TSDF ray-casting (added under ABI 28: new symbols only; csrc/tsdf.hip, csrc/tsdf_math.h; Python: TsdfVolume.raycast): the
+ * volume seen from a camera -- depth along the forward axis, the world-frame normal toward the free side and the colour of the
+ * first surface along each pixel's ray. sfgs_tsdf_raycast is ONE launch, a thread per pixel; tests/tsdf_raycast_np.py states the
+ * sequence in numpy and the kernel equals it byte for byte. Float64 on the stored float32 values, in the order written, nothing
+ * contracted; lerp(a, b, f) = a + f * (b - a).
+ *   1. ray of pixel (row, col): x = (col - cx_pix) / focal_x, y = (row - cy_pix) / focal_y, d[a] = (x M[a] + y M[3 + a]) + M[6 + a];
+ *      the point at depth z is p[a] = c[a] + z d[a] (M, c as in SfgsTsdfView).
+ *   2. clip to the box of voxel centres, per axis lo = origin + 0.5 voxel_size, hi = origin + (n - 0.5) voxel_size: with
+ *      d[a] == 0 the ray misses unless lo <= c[a] <= hi; otherwise t0 = (lo - c[a]) / d[a], t1 = (hi - c[a]) / d[a], swapped if
+ *      t0 > t1, then if (t0 > z0) z0 = t0, if (t1 < z1) z1 = t1, from z0 = near and z1 = far. The ray misses unless z0 <= z1 (NaN
+ *      fails). A volume with a dimension of 1 has no cell: every ray misses, nothing is launched.
+ *   3. samples z_k = z0 + (double)k step, k = 0 ... K - 1, K = floor((z1 - z0) / step) + 1, capped at 2^20 on the double.
+ *   4. a sample: per axis g = (p - origin) * inv_voxel - 0.5 with inv_voxel = 1.0 / voxel_size formed once on the host; i = floor(g)
+ *      clamped to [0, n - 2] on the double, f = g - i clamped to [0, 1]. It is VALID when the eight corner weights of cell i are
+ *      > 0 (extraction's rule). With v0 ... v7 the corner values (corner k at the offsets (k & 1, (k >> 1) & 1, (k >> 2) & 1)):
+ *        x00 = lerp(v0, v1, fx), x10 = lerp(v2, v3, fx), x01 = lerp(v4, v5, fx), x11 = lerp(v6, v7, fx),
+ *        y0 = lerp(x00, x10, fy), y1 = lerp(x01, x11, fy), val = lerp(y0, y1, fz);
+ *        gz = y1 - y0, gy = lerp(x10 - x00, x11 - x01, fz), gx = lerp(lerp(v1 - v0, v3 - v2, fy), lerp(v5 - v4, v7 - v6, fy), fz);
+ *      a colour channel takes the value's sequence on its plane.
+ *   5. the hit is the smallest k >= 1 whose sample is valid with val < 0 and whose predecessor k - 1 is valid with val >= 0
+ *      (a zero is outside, as in extraction). Nothing else ends a ray: not a first sample that is already negative, not an
+ *      unobserved gap, not a crossing from negative to positive.
+ *   6. with vp, vc the two values, w = vp / (vp - vc): depth = (float)(z_{k-1} + w (z_k - z_{k-1})); g = gp + w (gc - gp) per
+ *      component, len = sqrt((gx gx + gy gy) + gz gz), normal = (float)(g / len), zeros unless len > 0; rgb = (float)(cp + w (cc - cp)).
+ *      A pixel without a hit gets zeros in every output. No output reads an unobserved voxel.
+ *   7. empty-space skipping changes no byte. The table (sfgs_tsdf_skip_build, one launch, a workgroup per brick, no atomics) has
+ *      one byte per brick of 8 x 8 x 8 cells, laid out [bz][by][bx] over the (n - 1) cells per axis, non-zero when some voxel
+ *      of the brick's footprint -- voxels 8b ... min(8b + 8, n - 1) per axis -- has weight > 0 && tsdf < 0. A trilinear value
+ *      of non-negative corners is non-negative in this lerp form (rounding is monotone), so a sample whose cell lies in a brick
+ *      with a zero byte is never the negative end of a hit and is not evaluated. The march visits k in ascending order; from a
+ *      sample in such a brick it proposes a jump of j lattice steps from the ray's exit of the brick's slab and takes it only
+ *      after the cell of sample k + j has been recomputed and found in the same brick (a cell coordinate is monotone in k, so
+ *      equal ends mean an equal interior); otherwise it advances by one. A valid negative sample whose predecessor was skipped has
+ *      that predecessor evaluated on demand. The table describes the volume as it was when built; skip == NULL marches every sample.
+ *   depth   float32 [H][W]; normal float32 [3][H][W] or NULL; rgb float32 [3][H][W], NULL exactly when vol->rgb is.
+ *   step    measured along the forward axis, like the depths; the library refuses a step so small that the box diagonal
+ *           holds more than 2^20 of them.
+ * Refusals are SFGS_E_ARG, made before any GPU work: what SfgsTsdfVolume is refused for, a NULL pointer, a wrong struct_size,
+ * H or W < 1, H W > 2^30, a non-finite M, c or principal point, a focal length that is zero or not finite, near < 0 or not finite,
+ * far <= near or NaN, a step that is not finite and > 0 or too small, an rgb pointer that does not go with vol->rgb, a table
+ * smaller than sfgs_tsdf_skip_bytes. No profiler ids. */
+typedef struct SfgsTsdfRay {
+  uint32_t struct_size;          /* = sizeof(SfgsTsdfRay) */
+  int32_t H, W;
+  double M[9];                   /* world = cam @ M + c */
+  double c[3];
+  double cx_pix, cy_pix, focal_x, focal_y, near, far, step;
+  float* depth;                  /* device, [H][W] */
+  float* normal;                 /* device, [3][H][W], or NULL */
+  float* rgb;                    /* device, [3][H][W]; NULL exactly when the volume has no colours */
+} SfgsTsdfRay;
+size_t sfgs_tsdf_skip_bytes(int32_t nx, int32_t ny, int32_t nz);      /* 0: bad arguments (sfgs_last_error) */
+int sfgs_tsdf_skip_build(const SfgsTsdfVolume* vol, void* skip, size_t bytes, void* stream);
+int sfgs_tsdf_raycast(const SfgsTsdfVolume* vol, const SfgsTsdfRay* ray, const void* skip, size_t skip_bytes, void* stream);
+
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the
  * per-pixel tests, before the pixel saturated -- with blend weight w = alpha T:

@@ -1,4 +1,4 @@
-// tsdf.hip -- depth views -> a truncated signed distance volume -> a triangle soup: the surface the other geometry products
+// tsdf.hip -- depth views -> a truncated signed distance volume -> a triangle soup, or views ray-cast from it: the surface the other geometry products
 // (geometry.hip: a 2.5-D height grid; pointcloud.hip: unconnected points) do not give. The reference has no mesh step. The
 // per-voxel update and the per-cell marching-tetrahedra triangulation are tsdf_math.h's (built for the host too, by
 // tests/host_check/tsdf_check.cpp); include/sfgs.h states both sequences in words and tests/tsdf_np.py in numpy; this file is held
@@ -16,8 +16,19 @@
 //     2. tsdf_scan_kernel   ONE workgroup scans the counts exclusively, 1024 at a time with a carry, and leaves the total in *state;
 //     3. tsdf_emit_kernel   recomputes the cells, ranks their triangles inside the workgroup and writes the workgroup's run.
 //     The soup is ordered by cell, tetrahedron, triangle. A row at or beyond `capacity` is not written; the state counts it.
+//   ray-casting, ONE launch per view (tsdf_math.h: tsdf_ray_pixel; tests/tsdf_raycast_np.py in numpy, held to it byte for byte):
+//     tsdf_raycast_kernel<COLORS, NORMALS, SKIP>  a thread owns a pixel: its ray is cut to the box of voxel centres and marched on
+//       a lattice of depths; a sample gathers the eight voxels (and weights) of its cell into registers, static indices only; the
+//       hit is the first valid sample < 0 behind a valid sample >= 0. Gradient and colour of the two bracketing samples are
+//       gathered after the march, not in it. Rays diverge in length: a wave is an 8 x 8 tile of pixels (a workgroup 16 x 16), so
+//       its rays stay together and its gathers fall into a compact part of the volume. No LDS, no atomics, no barrier.
+//     tsdf_skip_kernel  the empty-space table: a workgroup per brick of 8^3 cells ORs `observed and inside` over the brick's
+//       footprint of at most 9^3 voxels (__syncthreads_or) and stores one byte. With SKIP the march does not evaluate samples in
+//       bricks whose byte is 0 and jumps over runs of them; the outputs are the same bytes.
 // Every index is range-checked before it is used: a voxel against the volume before its load and store, a pixel against its view's
-// H x W (on the doubles) before its load, a cell against the cell grid before its eight corners, a row against capacity.
+// H x W (on the doubles) before its load, a cell against the cell grid before its eight corners, a row against capacity; in the
+// ray-cast a cell comes out of a clamp to [0, n - 2] on the double, a brick is checked against the table's dims before its load,
+// a pixel against H x W before any load or store.
 // No profiler ids.
 #include "sfgs_internal.h"
 #include "tsdf_math.h"
@@ -189,6 +200,64 @@ tsdf_emit_kernel(TsdfCells g, TsdfMeshFrame f, const float* __restrict__ tsdf, c
   tsdf_cell_emit<COLORS>(f, val, col, x, y, z, vertices, colors, (long long)first, capacity);
 }
 
+// ---- ray-casting -----------------------------------------------------------------------------------------------------------------
+constexpr int TSDF_RAY_TILE = 16;                    // a workgroup is 16 x 16 pixels, a wave an 8 x 8 quarter of it
+static_assert(TSDF_RAY_TILE * TSDF_RAY_TILE == TSDF_THREADS && TSDF_WAVES == 4, "four 8 x 8 waves");
+
+// One workgroup per brick of 8^3 cells: its byte is non-zero when a voxel of the footprint (at most 9^3) is observed and inside.
+__global__ void __launch_bounds__(TSDF_THREADS)
+tsdf_skip_kernel(TsdfRayGrid g, const float* __restrict__ tsdf, const float* __restrict__ weight, unsigned char* __restrict__ skip) {
+  const unsigned per_z = (unsigned)(g.bx * g.by);
+  const unsigned bz = blockIdx.x / per_z, rest = blockIdx.x - bz * per_z;
+  const unsigned by = rest / (unsigned)g.bx, bx = rest - by * (unsigned)g.bx;
+  if (bz >= (unsigned)g.bz) return;                  // the whole workgroup: no thread reaches the barrier
+  const int lo[3] = {(int)bx * TSDF_SKIP_BRICK, (int)by * TSDF_SKIP_BRICK, (int)bz * TSDF_SKIP_BRICK};
+  const int n[3] = {g.nx, g.ny, g.nz};
+  int hi[3];                                         // the footprint's last voxel per axis
+#pragma unroll
+  for (int a = 0; a < 3; ++a) hi[a] = lo[a] + TSDF_SKIP_BRICK < n[a] - 1 ? lo[a] + TSDF_SKIP_BRICK : n[a] - 1;
+  constexpr int E = TSDF_SKIP_BRICK + 1;             // a full footprint is E^3 voxels: constant divisors, a partial one skips
+  int any = 0;
+  for (int t = (int)threadIdx.x; t < E * E * E; t += TSDF_THREADS) {
+    const int tz = t / (E * E), r = t - tz * (E * E);
+    const int ty = r / E, tx = r - ty * E;
+    const int x = lo[0] + tx, y = lo[1] + ty, z = lo[2] + tz;
+    if (x <= hi[0] && y <= hi[1] && z <= hi[2]) {       // hi < n: inside the volume
+      const long long p = ((long long)z * g.ny + y) * g.nx + x;
+      any |= tsdf_skip_flag(weight[p], tsdf[p]) ? 1 : 0;
+    }
+  }
+  any = __syncthreads_or(any);
+  if (threadIdx.x == 0) skip[blockIdx.x] = any ? 1 : 0;
+}
+
+// One thread per pixel; tiles are numbered row by row in blockIdx.x. The rays of a wave leave an 8 x 8 patch of the image, so
+// their gathers stay in a compact part of the volume. Grid and camera are kernel arguments: uniform, read by scalar loads.
+template <bool COLORS, bool NORMALS, bool SKIP>
+__global__ void __launch_bounds__(TSDF_THREADS)
+tsdf_raycast_kernel(TsdfRayGrid g, TsdfRayCamera cam, int H, int W, const float* __restrict__ tsdf, const float* __restrict__ weight,
+                    const float* __restrict__ rgb, const unsigned char* __restrict__ skip, float* __restrict__ depth,
+                    float* __restrict__ normal, float* __restrict__ colour) {
+  const unsigned tiles_x = (unsigned)((W + TSDF_RAY_TILE - 1) / TSDF_RAY_TILE);
+  const unsigned tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const int col = (int)(tile_x * TSDF_RAY_TILE + (wave & 1u) * 8u + (lane & 7u));
+  const int row = (int)(tile_y * TSDF_RAY_TILE + (wave >> 1) * 8u + (lane >> 3));
+  if (row >= H || col >= W) return;                  // before any load; no barrier follows
+  float dep, nrm[3], rgb_out[3];
+  tsdf_ray_pixel<COLORS, NORMALS, SKIP>(g, cam, row, col, tsdf, weight, rgb, skip, &dep, nrm, rgb_out, nullptr);
+  const long long P = (long long)H * W, p = (long long)row * W + col;
+  depth[p] = dep;
+  if (NORMALS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) normal[c * P + p] = nrm[c];
+  }
+  if (COLORS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) colour[c * P + p] = rgb_out[c];
+  }
+}
+
 }  // namespace sfgs
 
 using namespace sfgs;
@@ -299,5 +368,115 @@ extern "C" int sfgs_tsdf_extract(const SfgsTsdfVolume* vol, float* vertices, flo
                          (const float*)vol->rgb, (const unsigned long long*)blk, vertices, colors, (long long)capacity);
     SFGS_POST_LAUNCH("tsdf_emit", stream, 0);
   }
+  return SFGS_OK;
+}
+
+// ---- ray-casting -----------------------------------------------------------------------------------------------------------------
+namespace {
+
+TsdfRayGrid tsdf_ray_grid(const SfgsTsdfVolume* vol) {
+  TsdfRayGrid g;
+  g.nx = vol->nx; g.ny = vol->ny; g.nz = vol->nz;
+  g.bx = tsdf_skip_bricks(vol->nx); g.by = tsdf_skip_bricks(vol->ny); g.bz = tsdf_skip_bricks(vol->nz);
+  for (int a = 0; a < 3; ++a) g.origin[a] = vol->origin[a];
+  g.voxel_size = vol->voxel_size;
+  g.inv_voxel = 1.0 / vol->voxel_size;
+  return g;
+}
+
+inline size_t tsdf_skip_table_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  return (size_t)tsdf_skip_bricks(nx) * (size_t)tsdf_skip_bricks(ny) * (size_t)tsdf_skip_bricks(nz);      // <= 2^30
+}
+
+inline bool tsdf_has_cells(const SfgsTsdfVolume* vol) { return vol->nx >= 2 && vol->ny >= 2 && vol->nz >= 2; }
+
+template <bool COLORS, bool NORMALS, bool SKIP>
+void tsdf_raycast_launch(dim3 grid, hipStream_t stream, const TsdfRayGrid& g, const TsdfRayCamera& cam, const SfgsTsdfVolume* vol,
+                         const SfgsTsdfRay* ray, const unsigned char* skip) {
+  hipLaunchKernelGGL((tsdf_raycast_kernel<COLORS, NORMALS, SKIP>), grid, dim3(TSDF_THREADS), 0, stream, g, cam, ray->H, ray->W,
+                     (const float*)vol->tsdf, (const float*)vol->weight, (const float*)vol->rgb, skip, ray->depth, ray->normal, ray->rgb);
+}
+
+template <bool COLORS, bool NORMALS>
+void tsdf_raycast_launch(dim3 grid, hipStream_t stream, const TsdfRayGrid& g, const TsdfRayCamera& cam, const SfgsTsdfVolume* vol,
+                         const SfgsTsdfRay* ray, const unsigned char* skip) {
+  if (skip) tsdf_raycast_launch<COLORS, NORMALS, true>(grid, stream, g, cam, vol, ray, skip);
+  else tsdf_raycast_launch<COLORS, NORMALS, false>(grid, stream, g, cam, vol, ray, skip);
+}
+
+}  // namespace
+
+extern "C" size_t sfgs_tsdf_skip_bytes(int32_t nx, int32_t ny, int32_t nz) {
+  if (tsdf_check_dims("sfgs_tsdf_skip_bytes", nx, ny, nz)) return 0;
+  return tsdf_skip_table_bytes(nx, ny, nz);
+}
+
+extern "C" int sfgs_tsdf_skip_build(const SfgsTsdfVolume* vol, void* skip, size_t bytes, void* stream_) {
+  if (const int rc = tsdf_check_volume(vol)) return rc;
+  SFGS_REQUIRE(skip, SFGS_E_ARG, "sfgs_tsdf_skip_build: NULL table");
+  const size_t need = tsdf_skip_table_bytes(vol->nx, vol->ny, vol->nz);
+  SFGS_REQUIRE(bytes >= need, SFGS_E_ARG, "tsdf skip table too small: %zu < %zu", bytes, need);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!tsdf_has_cells(vol)) {                              // no cell, no ray-cast kernel will read the table: one zero byte
+    SFGS_CHECK_HIP(hipMemsetAsync(skip, 0, need, stream));
+    return SFGS_OK;
+  }
+  const TsdfRayGrid g = tsdf_ray_grid(vol);
+  hipLaunchKernelGGL(tsdf_skip_kernel, dim3((unsigned)need), dim3(TSDF_THREADS), 0, stream, g, (const float*)vol->tsdf,
+                     (const float*)vol->weight, (unsigned char*)skip);
+  SFGS_POST_LAUNCH("tsdf_skip", stream, 0);
+  return SFGS_OK;
+}
+
+extern "C" int sfgs_tsdf_raycast(const SfgsTsdfVolume* vol, const SfgsTsdfRay* ray, const void* skip, size_t skip_bytes, void* stream_) {
+  if (const int rc = tsdf_check_volume(vol)) return rc;
+  SFGS_REQUIRE(ray, SFGS_E_ARG, "NULL SfgsTsdfRay");
+  SFGS_REQUIRE(ray->struct_size == sizeof(SfgsTsdfRay), SFGS_E_ARG, "SfgsTsdfRay.struct_size %u, expected %zu", ray->struct_size,
+               sizeof(SfgsTsdfRay));
+  SFGS_REQUIRE(ray->H > 0 && ray->W > 0, SFGS_E_ARG, "SfgsTsdfRay: H %d, W %d", ray->H, ray->W);
+  SFGS_REQUIRE((long long)ray->H * ray->W <= (1ll << 30), SFGS_E_ARG, "SfgsTsdfRay: H * W must not exceed 2^30, got %d x %d", ray->H, ray->W);
+  for (int k = 0; k < 9; ++k) SFGS_REQUIRE(fabs(ray->M[k]) < INFINITY, SFGS_E_ARG, "SfgsTsdfRay.M[%d] %g: finite", k, ray->M[k]);
+  for (int k = 0; k < 3; ++k) SFGS_REQUIRE(fabs(ray->c[k]) < INFINITY, SFGS_E_ARG, "SfgsTsdfRay.c[%d] %g: finite", k, ray->c[k]);
+  SFGS_REQUIRE(fabs(ray->cx_pix) < INFINITY && fabs(ray->cy_pix) < INFINITY, SFGS_E_ARG, "SfgsTsdfRay: principal point %g, %g: finite",
+               ray->cx_pix, ray->cy_pix);
+  SFGS_REQUIRE(ray->focal_x != 0.0 && ray->focal_y != 0.0 && fabs(ray->focal_x) < INFINITY && fabs(ray->focal_y) < INFINITY, SFGS_E_ARG,
+               "SfgsTsdfRay: focal %g, %g: finite and non-zero", ray->focal_x, ray->focal_y);
+  SFGS_REQUIRE(ray->near >= 0.0 && ray->near < INFINITY, SFGS_E_ARG, "SfgsTsdfRay.near %g: finite and >= 0", ray->near);
+  SFGS_REQUIRE(ray->far > ray->near, SFGS_E_ARG, "SfgsTsdfRay.far %g: above near %g", ray->far, ray->near);      // NaN fails
+  SFGS_REQUIRE(ray->step > 0.0 && ray->step < INFINITY, SFGS_E_ARG, "SfgsTsdfRay.step %g: finite and > 0", ray->step);
+  const double ex = (vol->nx - 1) * vol->voxel_size, ey = (vol->ny - 1) * vol->voxel_size, ez = (vol->nz - 1) * vol->voxel_size;
+  const double diagonal = sqrt(ex * ex + ey * ey + ez * ez);
+  SFGS_REQUIRE(diagonal / ray->step <= (double)TSDF_RAY_MAX_SAMPLES, SFGS_E_ARG,
+               "SfgsTsdfRay.step %g: the box diagonal %g holds more than 2^20 steps", ray->step, diagonal);
+  SFGS_REQUIRE(ray->depth, SFGS_E_ARG, "SfgsTsdfRay: NULL depth");
+  SFGS_REQUIRE((vol->rgb == nullptr) == (ray->rgb == nullptr), SFGS_E_ARG, "sfgs_tsdf_raycast: SfgsTsdfVolume.rgb and SfgsTsdfRay.rgb come together");
+  const size_t need = tsdf_skip_table_bytes(vol->nx, vol->ny, vol->nz);
+  SFGS_REQUIRE(!skip || skip_bytes >= need, SFGS_E_ARG, "tsdf skip table too small: %zu < %zu", skip_bytes, need);
+  hipStream_t stream = (hipStream_t)stream_;
+  const long long P = (long long)ray->H * ray->W;
+  if (!tsdf_has_cells(vol)) {                              // every ray misses: the outputs of a miss, and no launch
+    SFGS_CHECK_HIP(hipMemsetAsync(ray->depth, 0, (size_t)P * 4, stream));
+    if (ray->normal) SFGS_CHECK_HIP(hipMemsetAsync(ray->normal, 0, (size_t)P * 12, stream));
+    if (ray->rgb) SFGS_CHECK_HIP(hipMemsetAsync(ray->rgb, 0, (size_t)P * 12, stream));
+    return SFGS_OK;
+  }
+  const TsdfRayGrid g = tsdf_ray_grid(vol);
+  TsdfRayCamera cam;
+  for (int k = 0; k < 9; ++k) cam.M[k] = ray->M[k];
+  for (int k = 0; k < 3; ++k) cam.c[k] = ray->c[k];
+  cam.cx_pix = ray->cx_pix; cam.cy_pix = ray->cy_pix; cam.focal_x = ray->focal_x; cam.focal_y = ray->focal_y;
+  cam.near = ray->near; cam.far = ray->far; cam.step = ray->step;
+  const long long tiles = (long long)((ray->W + TSDF_RAY_TILE - 1) / TSDF_RAY_TILE) * ((ray->H + TSDF_RAY_TILE - 1) / TSDF_RAY_TILE);
+  SFGS_REQUIRE(tiles <= 0x7fffffffll, SFGS_E_ARG, "sfgs_tsdf_raycast: %lld workgroups", tiles);
+  const dim3 grid((unsigned)tiles);
+  const unsigned char* table = (const unsigned char*)skip;
+  if (ray->rgb) {
+    if (ray->normal) tsdf_raycast_launch<true, true>(grid, stream, g, cam, vol, ray, table);
+    else tsdf_raycast_launch<true, false>(grid, stream, g, cam, vol, ray, table);
+  } else {
+    if (ray->normal) tsdf_raycast_launch<false, true>(grid, stream, g, cam, vol, ray, table);
+    else tsdf_raycast_launch<false, false>(grid, stream, g, cam, vol, ray, table);
+  }
+  SFGS_POST_LAUNCH("tsdf_raycast", stream, 0);
   return SFGS_OK;
 }

@@ -1,7 +1,8 @@
-// tsdf_math.h -- the per-voxel update of TSDF fusion and the per-cell marching-tetrahedra triangulation, written ONCE: tsdf.hip
-// runs them on the device, tests/host_check/tsdf_check.cpp builds them with g++ for the CPU suite (GEO_FN: geo_unproject.h), and
-// tests/tsdf_np.py states both in numpy; the three are held to each other byte for byte. include/sfgs.h gives the sequences in
-// words. Nothing is contracted (-ffp-contract=off on both compilers): products, sums and quotients in the order written.
+// tsdf_math.h -- the per-voxel update of TSDF fusion, the per-cell marching-tetrahedra triangulation and the per-pixel ray-cast,
+// written ONCE: tsdf.hip runs them on the device, tests/host_check/tsdf_check.cpp and tsdf_raycast_check.cpp build them with g++
+// for the CPU suite (GEO_FN: geo_unproject.h), and tests/tsdf_np.py and tests/tsdf_raycast_np.py state them in numpy; the three
+// are held to each other byte for byte. include/sfgs.h gives the sequences in words. Nothing is contracted (-ffp-contract=off on
+// both compilers): products, sums and quotients in the order written.
 #pragma once
 #include "geo_unproject.h"
 
@@ -195,6 +196,286 @@ GEO_FN int tsdf_cell_emit(const TsdfMeshFrame& f, const float (&val)[8], const f
   GEO_UNROLL
   for (int t = 0; t < 6; ++t) n += tsdf_tet_emit<COLORS>(f, val, col, t, x, y, z, vertices, colors, first + n, capacity);
   return n;
+}
+
+// ---- ray-casting -----------------------------------------------------------------------------------------------------------------
+// A camera ray marched through the volume on a lattice of depths; the first sign change from >= 0 to < 0 between two valid samples
+// is the surface. include/sfgs.h states the sequence in words, tests/tsdf_raycast_np.py in numpy (the uniform march only);
+// tsdf_raycast_kernel and tests/host_check/tsdf_raycast_check.cpp run the functions below. Float64 on the stored float32 values.
+constexpr int TSDF_RAY_MAX_SAMPLES = 1 << 20;   // samples per ray
+constexpr int TSDF_SKIP_BRICK = 8;              // cells per axis of a brick of the empty-space table
+
+struct TsdfRayGrid {
+  int nx, ny, nz;                               // every one >= 2: the caller launches nothing otherwise
+  int bx, by, bz;                               // bricks per axis: tsdf_skip_bricks(n)
+  double origin[3], voxel_size, inv_voxel;      // inv_voxel = 1.0 / voxel_size, formed once on the host
+};
+
+struct TsdfRayCamera {
+  double M[9], c[3];
+  double cx_pix, cy_pix, focal_x, focal_y, near, far, step;
+};
+
+// What the host build counts; the kernel passes nullptr.
+struct TsdfRayCounters {
+  long long samples;                            // samples whose eight corners were loaded
+  long long jumps;                              // accepted jumps
+  long long longest;                            // lattice steps of the longest one (it stays in one brick)
+  long long longest_run;                        // most consecutive samples of a ray not evaluated: jumps and single steps, brick after brick
+};
+
+// constexpr: the host's launch code calls it too
+constexpr int tsdf_skip_bricks(int n) { return n < 2 ? 1 : (n - 1 + TSDF_SKIP_BRICK - 1) / TSDF_SKIP_BRICK; }
+
+// A voxel that sets its bricks' bytes: observed and inside.
+GEO_FN bool tsdf_skip_flag(float weight, float value) { return weight > 0.f && value < 0.f; }
+
+GEO_FN double tsdf_lerp(double a, double b, double f) { return a + f * (b - a); }
+
+// Direction of pixel (row, col): the point at depth z along the forward axis is c + z * d.
+GEO_FN void tsdf_ray_direction(const TsdfRayCamera& cam, int row, int col, double (&d)[3]) {
+  const double x = ((double)col - cam.cx_pix) / cam.focal_x;
+  const double y = ((double)row - cam.cy_pix) / cam.focal_y;
+  GEO_UNROLL
+  for (int a = 0; a < 3; ++a) d[a] = (x * cam.M[a] + y * cam.M[3 + a]) + cam.M[6 + a];
+}
+
+// [near, far] cut to the box of voxel centres -> false for a miss (NaN too).
+GEO_FN bool tsdf_ray_clip(const TsdfRayGrid& g, const TsdfRayCamera& cam, const double (&d)[3], double* z0_out, double* z1_out) {
+  const int n[3] = {g.nx, g.ny, g.nz};
+  double z0 = cam.near, z1 = cam.far;
+  bool inside = true;
+  GEO_UNROLL
+  for (int a = 0; a < 3; ++a) {
+    const double lo = g.origin[a] + 0.5 * g.voxel_size, hi = g.origin[a] + ((double)n[a] - 0.5) * g.voxel_size;
+    if (d[a] == 0.0) {
+      inside = inside && lo <= cam.c[a] && cam.c[a] <= hi;
+    } else {
+      double t0 = (lo - cam.c[a]) / d[a], t1 = (hi - cam.c[a]) / d[a];
+      if (t0 > t1) { const double t = t0; t0 = t1; t1 = t; }
+      if (t0 > z0) z0 = t0;
+      if (t1 < z1) z1 = t1;
+    }
+  }
+  *z0_out = z0; *z1_out = z1;
+  return inside && z0 <= z1;
+}
+
+// Samples on [z0, z1]: floor((z1 - z0) / step) + 1, capped on the double (a NaN quotient takes the cap).
+GEO_FN int tsdf_ray_samples(double z0, double z1, double step) {
+  const double q = floor((z1 - z0) / step);
+  return q < (double)(TSDF_RAY_MAX_SAMPLES - 1) ? (int)q + 1 : TSDF_RAY_MAX_SAMPLES;
+}
+
+GEO_FN double tsdf_ray_depth(double z0, int k, double step) { return z0 + (double)k * step; }
+
+// The cell of the point at depth z and the position inside it: i in [0, n - 2] and f in [0, 1], clamped on the doubles.
+GEO_FN void tsdf_ray_cell(const TsdfRayGrid& g, const TsdfRayCamera& cam, const double (&d)[3], double z, int (&cell)[3], double (&f)[3]) {
+  const int n[3] = {g.nx, g.ny, g.nz};
+  GEO_UNROLL
+  for (int a = 0; a < 3; ++a) {
+    const double p = cam.c[a] + z * d[a];
+    const double q = (p - g.origin[a]) * g.inv_voxel - 0.5;
+    double i = floor(q);
+    if (!(i >= 0.0)) i = 0.0;                                             // NaN too
+    if (i > (double)(n[a] - 2)) i = (double)(n[a] - 2);
+    double r = q - i;
+    if (!(r >= 0.0)) r = 0.0;
+    if (r > 1.0) r = 1.0;
+    cell[a] = (int)i;
+    f[a] = r;
+  }
+}
+
+// The eight corners of a cell (in range: tsdf_ray_cell clamped it) from one plane of the volume.
+GEO_FN void tsdf_ray_corners(const TsdfRayGrid& g, const float* __restrict__ plane, const int (&cell)[3], float (&v)[8]) {
+  const long long row = g.nx, slab = (long long)g.nx * g.ny;
+  const long long base = ((long long)cell[2] * g.ny + cell[1]) * g.nx + cell[0];
+  GEO_UNROLL
+  for (int k = 0; k < 8; ++k) v[k] = plane[base + (k & 1) + ((k >> 1) & 1) * row + ((k >> 2) & 1) * slab];
+}
+
+// Extraction's rule for a used cell.
+GEO_FN bool tsdf_ray_valid(const float (&w)[8]) {
+  bool ok = true;
+  GEO_UNROLL
+  for (int k = 0; k < 8; ++k) ok = ok && w[k] > 0.f;
+  return ok;
+}
+
+GEO_FN double tsdf_trilinear(const float (&v)[8], const double (&f)[3]) {
+  const double x00 = tsdf_lerp(v[0], v[1], f[0]), x10 = tsdf_lerp(v[2], v[3], f[0]);
+  const double x01 = tsdf_lerp(v[4], v[5], f[0]), x11 = tsdf_lerp(v[6], v[7], f[0]);
+  const double y0 = tsdf_lerp(x00, x10, f[1]), y1 = tsdf_lerp(x01, x11, f[1]);
+  return tsdf_lerp(y0, y1, f[2]);
+}
+
+// The gradient of the trilinear value in index units.
+GEO_FN void tsdf_trilinear_gradient(const float (&v)[8], const double (&f)[3], double (&grad)[3]) {
+  const double v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3], v4 = v[4], v5 = v[5], v6 = v[6], v7 = v[7];
+  const double x00 = tsdf_lerp(v0, v1, f[0]), x10 = tsdf_lerp(v2, v3, f[0]);
+  const double x01 = tsdf_lerp(v4, v5, f[0]), x11 = tsdf_lerp(v6, v7, f[0]);
+  const double y0 = tsdf_lerp(x00, x10, f[1]), y1 = tsdf_lerp(x01, x11, f[1]);
+  grad[2] = y1 - y0;
+  grad[1] = tsdf_lerp(x10 - x00, x11 - x01, f[2]);
+  grad[0] = tsdf_lerp(tsdf_lerp(v1 - v0, v3 - v2, f[1]), tsdf_lerp(v5 - v4, v7 - v6, f[1]), f[2]);
+}
+
+// Sample k of a ray -> valid?, and its value when it is.
+GEO_FN bool tsdf_ray_sample(const TsdfRayGrid& g, const float* __restrict__ tsdf, const float* __restrict__ weight, const int (&cell)[3],
+                            const double (&f)[3], double* value, TsdfRayCounters* n) {
+  float w[8], v[8];
+  tsdf_ray_corners(g, weight, cell, w);
+  tsdf_ray_corners(g, tsdf, cell, v);
+  if (n) ++n->samples;
+  *value = tsdf_trilinear(v, f);
+  return tsdf_ray_valid(w);
+}
+
+// How many lattice steps a sample at (cell, f) may advance and stay in its cell's brick, out of `left`: from where the ray leaves
+// the brick's slab along each axis (inv_dq: lattice steps per cell), less one. A proposal only: the caller tests the far end.
+GEO_FN int tsdf_ray_jump(const int (&cell)[3], const double (&f)[3], const double (&inv_dq)[3], int left) {
+  double t = (double)left;
+  GEO_UNROLL
+  for (int a = 0; a < 3; ++a) {
+    const int lo = cell[a] & ~(TSDF_SKIP_BRICK - 1);
+    const double q = (double)cell[a] + f[a];
+    if (inv_dq[a] > 0.0) {
+      const double e = ((double)(lo + TSDF_SKIP_BRICK) - q) * inv_dq[a];
+      if (e < t) t = e;
+    } else if (inv_dq[a] < 0.0) {
+      const double e = ((double)lo - q) * inv_dq[a];
+      if (e < t) t = e;
+    }
+  }
+  return t >= 2.0 ? (int)t - 1 : 0;                                        // t <= left <= 2^20; NaN gives 0
+}
+
+// The march. -> the hit: the smallest k >= 1 whose sample is valid with a value < 0 and whose predecessor is valid with a value
+// >= 0 (*vp, *vc: the two values), or 0 for none. SKIP: samples whose cell lies in a brick with a zero byte are not evaluated
+// -- no corner of such a cell is inside, so its value is not below 0 -- and runs of them in one brick are jumped over; the
+// predecessor of a negative sample is evaluated on demand. The same hit and the same two values either way.
+template <bool SKIP>
+GEO_FN int tsdf_ray_march(const TsdfRayGrid& g, const TsdfRayCamera& cam, const double (&d)[3], double z0, int K,
+                          const float* __restrict__ tsdf, const float* __restrict__ weight, const unsigned char* __restrict__ skip,
+                          double* vp, double* vc, TsdfRayCounters* n) {
+  int cell[3];
+  double f[3], value;
+  if (!SKIP) {
+    bool before = false;                                                   // sample k - 1 is valid with a value >= 0
+    double prev = 0.0;
+    for (int k = 0; k < K; ++k) {
+      tsdf_ray_cell(g, cam, d, tsdf_ray_depth(z0, k, cam.step), cell, f);
+      const bool valid = tsdf_ray_sample(g, tsdf, weight, cell, f, &value, n);
+      if (valid && value < 0.0 && before) { *vp = prev; *vc = value; return k; }
+      before = valid && value >= 0.0;
+      prev = value;
+    }
+    return 0;
+  }
+  double inv_dq[3];                                                        // lattice steps per cell along each axis
+  GEO_UNROLL
+  for (int a = 0; a < 3; ++a) {
+    const double dq = cam.step * d[a] * g.inv_voxel;
+    inv_dq[a] = dq != 0.0 ? 1.0 / dq : 0.0;
+  }
+  int known = -1;                                                          // the sample that `before` and `prev` speak of
+  long long run = 0;                                                       // counted only: samples passed since the last evaluation
+  bool before = false;
+  double prev = 0.0;
+  int k = 0;
+  while (k < K) {
+    tsdf_ray_cell(g, cam, d, tsdf_ray_depth(z0, k, cam.step), cell, f);
+    const int b[3] = {cell[0] / TSDF_SKIP_BRICK, cell[1] / TSDF_SKIP_BRICK, cell[2] / TSDF_SKIP_BRICK};
+    const bool in_table = b[0] < g.bx && b[1] < g.by && b[2] < g.bz;       // cell >= 0: the clamp
+    if (in_table && skip[((long long)b[2] * g.by + b[1]) * g.bx + b[0]] == 0) {
+      const int j = tsdf_ray_jump(cell, f, inv_dq, K - 1 - k);
+      int step_k = 1;
+      if (j >= 1) {                                                        // accepted only if sample k + j is in the same brick:
+        int far_cell[3];                                                   // a cell coordinate is monotone in k
+        double far_f[3];
+        tsdf_ray_cell(g, cam, d, tsdf_ray_depth(z0, k + j, cam.step), far_cell, far_f);
+        if (far_cell[0] / TSDF_SKIP_BRICK == b[0] && far_cell[1] / TSDF_SKIP_BRICK == b[1] && far_cell[2] / TSDF_SKIP_BRICK == b[2]) {
+          step_k = j + 1;
+          if (n) { ++n->jumps; if (j > n->longest) n->longest = j; }
+        }
+      }
+      k += step_k;
+      if (n) { run += step_k; if (run > n->longest_run) n->longest_run = run; }
+      continue;
+    }
+    run = 0;
+    const bool valid = tsdf_ray_sample(g, tsdf, weight, cell, f, &value, n);
+    if (valid && value < 0.0 && k >= 1) {
+      if (known != k - 1) {
+        int pc[3];
+        double pf[3];
+        tsdf_ray_cell(g, cam, d, tsdf_ray_depth(z0, k - 1, cam.step), pc, pf);
+        const bool pvalid = tsdf_ray_sample(g, tsdf, weight, pc, pf, &prev, n);
+        before = pvalid && prev >= 0.0;
+      }
+      if (before) { *vp = prev; *vc = value; return k; }
+    }
+    known = k;
+    before = valid && value >= 0.0;
+    prev = value;
+    ++k;
+  }
+  return 0;
+}
+
+// Depth, normal and colour of the hit between samples k - 1 and k with the values vp >= 0 > vc. Both ends are valid samples.
+template <bool COLORS, bool NORMALS>
+GEO_FN void tsdf_ray_shade(const TsdfRayGrid& g, const TsdfRayCamera& cam, const double (&d)[3], double z0, int k, double vp, double vc,
+                           const float* __restrict__ tsdf, const float* __restrict__ rgb, float* depth, float (&normal)[3],
+                           float (&colour)[3]) {
+  const double zp = tsdf_ray_depth(z0, k - 1, cam.step), zc = tsdf_ray_depth(z0, k, cam.step);
+  const double w = vp / (vp - vc);
+  *depth = (float)(zp + w * (zc - zp));
+  if (!COLORS && !NORMALS) return;
+  int cp[3], cc[3];
+  double fp[3], fc[3];
+  tsdf_ray_cell(g, cam, d, zp, cp, fp);
+  tsdf_ray_cell(g, cam, d, zc, cc, fc);
+  float a[8], b[8];
+  if (NORMALS) {
+    double gp[3], gc[3], gr[3];
+    tsdf_ray_corners(g, tsdf, cp, a);
+    tsdf_ray_corners(g, tsdf, cc, b);
+    tsdf_trilinear_gradient(a, fp, gp);
+    tsdf_trilinear_gradient(b, fc, gc);
+    GEO_UNROLL
+    for (int i = 0; i < 3; ++i) gr[i] = gp[i] + w * (gc[i] - gp[i]);
+    const double len = sqrt((gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2]);
+    GEO_UNROLL
+    for (int i = 0; i < 3; ++i) normal[i] = len > 0.0 ? (float)(gr[i] / len) : 0.f;
+  }
+  if (COLORS) {
+    const long long nvox = (long long)g.nx * g.ny * g.nz;
+    GEO_UNROLL
+    for (int c = 0; c < 3; ++c) {
+      tsdf_ray_corners(g, rgb + c * nvox, cp, a);
+      tsdf_ray_corners(g, rgb + c * nvox, cc, b);
+      const double p = tsdf_trilinear(a, fp), q = tsdf_trilinear(b, fc);
+      colour[c] = (float)(p + w * (q - p));
+    }
+  }
+}
+
+// One pixel, start to end: zeros for a ray without a hit. skip is read only with SKIP.
+template <bool COLORS, bool NORMALS, bool SKIP>
+GEO_FN void tsdf_ray_pixel(const TsdfRayGrid& g, const TsdfRayCamera& cam, int row, int col, const float* __restrict__ tsdf,
+                           const float* __restrict__ weight, const float* __restrict__ rgb, const unsigned char* __restrict__ skip,
+                           float* depth, float (&normal)[3], float (&colour)[3], TsdfRayCounters* n) {
+  *depth = 0.f;
+  GEO_UNROLL
+  for (int i = 0; i < 3; ++i) normal[i] = colour[i] = 0.f;
+  double d[3], z0, z1, vp = 0.0, vc = 0.0;
+  tsdf_ray_direction(cam, row, col, d);
+  if (!tsdf_ray_clip(g, cam, d, &z0, &z1)) return;
+  const int K = tsdf_ray_samples(z0, z1, cam.step);
+  const int k = tsdf_ray_march<SKIP>(g, cam, d, z0, K, tsdf, weight, skip, &vp, &vc, n);
+  if (k >= 1) tsdf_ray_shade<COLORS, NORMALS>(g, cam, d, z0, k, vp, vc, tsdf, rgb, depth, normal, colour);
 }
 
 }  // namespace sfgs

@@ -169,6 +169,13 @@ class SfgsTsdfVolume(C.Structure):
                 ("weight", C.c_void_p), ("rgb", C.c_void_p)]
 
 
+class SfgsTsdfRay(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_double * 9), ("c", C.c_double * 3),
+                ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double),
+                ("near", C.c_double), ("far", C.c_double), ("step", C.c_double), ("depth", C.c_void_p), ("normal", C.c_void_p),
+                ("rgb", C.c_void_p)]
+
+
 class SfgsConsistencyArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("ref", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("min_views", C.c_int32), ("table", C.c_void_p), ("rel_tol", C.c_double), ("px_tol2", C.c_double)]
@@ -254,6 +261,9 @@ SYMBOLS = {
     "sfgs_tsdf_integrate": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _I32, _V]),
     "sfgs_tsdf_scratch_bytes": (_SZ, [_I32, _I32, _I32]),
     "sfgs_tsdf_extract": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _V, _I64, _V, _V, _SZ, _V]),
+    "sfgs_tsdf_skip_bytes": (_SZ, [_I32, _I32, _I32]),
+    "sfgs_tsdf_skip_build": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _SZ, _V]),
+    "sfgs_tsdf_raycast": (C.c_int, [C.POINTER(SfgsTsdfVolume), C.POINTER(SfgsTsdfRay), _V, _SZ, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

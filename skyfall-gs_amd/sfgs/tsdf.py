@@ -21,6 +21,23 @@ diagonal, no ambiguous case, a closed surface wherever the volume was observed. 
 voxels in a canonical order, so the soup welds by byte equality (TriangleSoup.weld). Triangles wind so that their normal points
 toward positive distances (the free side).
 
+Ray-casting is the third step: the volume seen from a camera, for a preview of the fused surface, a multi-view-consistent
+depth map for a camera that was never rendered, or a pixel-for-pixel comparison with a Gaussian render's depth.
+
+    view = vol.raycast(camera, 1024, 1024)                             # one launch, plus one for the empty-space table
+    view.depth, view.normal, view.rgb                                  # [1,H,W], [3,H,W], [3,H,W]; zeros where no surface was found
+    skip = vol.ray_skip()                                              # the table, reusable while the volume is unchanged
+    views = [vol.raycast(cam, 1024, 1024, skip=skip) for cam in cameras]
+
+A thread owns a pixel and marches its ray through the box of voxel centres on a lattice of depths `step` apart (voxel_size by
+default, measured along the camera's forward axis like the project's depth maps), trilinear on the eight voxels around each
+sample. The hit is the first pair of consecutive samples, both with all eight voxels observed, whose values go from >= 0 to
+< 0; depth, normal (the trilinear gradient, unit length, world frame, toward the free side) and colour are interpolated
+between the two. Empty-space skipping -- a byte per brick of 8 x 8 x 8 cells that says whether any of its voxels is observed and
+inside; samples in bricks without one are jumped over -- changes no byte: skip=False, skip=None and a prebuilt table agree, and
+the kernel equals the numpy restatement tests/tsdf_raycast_np.py byte for byte. Orthographic cameras, several views per launch
+and gradients through the ray-cast are not there.
+
 There is no sparse or hashed volume, no mesh simplification and no torch fallback: without the HIP library every operator raises."""
 import math
 import os
@@ -32,7 +49,7 @@ from . import _call
 from . import _lib as L
 from .geometry import _check_view, _u8, _vec
 
-__all__ = ["TsdfVolume", "TriangleSoup", "MAX_VIEWS", "MAX_VOXELS"]
+__all__ = ["TsdfVolume", "TriangleSoup", "RayView", "RaySkip", "MAX_VIEWS", "MAX_VOXELS"]
 
 MAX_VIEWS = 256
 MAX_VOXELS = 1 << 30
@@ -196,6 +213,102 @@ class TsdfVolume:
             L.check(lib.sfgs_tsdf_extract(L.C.byref(vol), L.ptr(vertices), L.ptr(colors), capacity, L.ptr(state), L.ptr(scratch),
                                           scratch.numel(), _call.stream(self.device)))
         return TriangleSoup(vertices, colors, state, capacity)
+
+    def ray_skip(self):
+        """-> RaySkip: the empty-space table of the volume's PRESENT state for raycast(skip=...), one byte per brick of 8 x 8 x 8
+        cells, non-zero where a voxel of the brick is observed and inside. One launch. It may be reused until the volume changes
+        (add_views, load, reset); raycast cannot tell a stale one."""
+        lib = L.load()
+        nbytes = lib.sfgs_tsdf_skip_bytes(*self.dims)
+        if nbytes == 0:
+            raise RuntimeError(f"libsfgs: {lib.sfgs_last_error().decode(errors='replace')}")
+        bricks = tuple(1 if n < 2 else (n + 6) // 8 for n in reversed(self.dims))
+        assert nbytes == bricks[0] * bricks[1] * bricks[2], (nbytes, bricks)
+        table = torch.empty(bricks, dtype=torch.uint8, device=self.device)
+        vol = self._struct()
+        with torch.cuda.device(self.device):
+            L.check(lib.sfgs_tsdf_skip_build(L.C.byref(vol), L.ptr(table), nbytes, _call.stream(self.device)))
+        return RaySkip(table, self.dims)
+
+    def raycast(self, camera, height, width, step=None, near=0.0, far=math.inf, normals=True, skip=None, out=None):
+        """-> RayView: the volume seen from `camera` at height x width pixels -- depth along the forward axis (0 where the ray
+        finds no surface), the unit normal toward the free side in the world frame and, when the volume keeps colours, the
+        colour -- with ONE launch and nothing read back. camera: read as add_views reads one (R, T, focal_x, focal_y; cx, cy
+        default to 0). step: the spacing of the samples along the forward axis, voxel_size by default; near, far: the range of
+        depths. A ray hits between the first two consecutive observed samples whose values go from >= 0 to < 0. skip: None
+        builds the empty-space table in the call (one more launch), False marches every sample, a ray_skip() result is used as
+        given; the three give the same bytes. out: a RayView of an earlier call with the same arguments, written again."""
+        for name, v in (("height", height), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        H, W = int(height), int(width)
+        if H * W > 1 << 30:
+            raise ValueError(f"height * width must not exceed 2^30, got {H} x {W}")
+        step = self.voxel_size if step is None else _positive(step, "step")
+        near = _positive(near, "near", at_least=0.0)
+        far = _positive(far, "far", allow_inf=True)
+        if not far > near:
+            raise ValueError(f"far must be above near, got near {near}, far {far}")
+        diagonal = self.voxel_size * math.sqrt(sum((n - 1) ** 2 for n in self.dims))
+        if diagonal / step > 1 << 20:
+            raise ValueError(f"step {step}: the volume's diagonal {diagonal} holds more than 2^20 steps")
+        if not (skip is None or skip is False or isinstance(skip, RaySkip)):
+            raise ValueError(f"skip must be None, False or a ray_skip() result, got {skip!r}")
+        if isinstance(skip, RaySkip):
+            if skip.dims != self.dims:
+                raise ValueError(f"skip was made for dims {skip.dims}, the volume has {self.dims}")
+            _call.same_device(self.device, "device", skip=skip.table)
+        if not isinstance(normals, (bool, np.bool_)):
+            raise ValueError(f"normals must be a bool, got {normals!r}")
+        normals = bool(normals)
+        if out is not None:
+            if not isinstance(out, RayView):
+                raise ValueError(f"out must be a RayView, got {out!r}")
+            if (out.normal is not None) != normals or (out.rgb is not None) != self.colors:
+                raise ValueError("out was made with other normals or by a volume with other colours")
+            _call.check_tensor("out.depth", out.depth, f"[1,{H},{W}]", lambda t: tuple(t.shape) == (1, H, W) and t.is_contiguous())
+            for name, t in (("out.normal", out.normal), ("out.rgb", out.rgb)):
+                _call.check_tensor(name, t, f"[3,{H},{W}]", lambda t: tuple(t.shape) == (3, H, W) and t.is_contiguous(), none_ok=True)
+        try:
+            cam = (camera.R, camera.T, camera.focal_x, camera.focal_y, getattr(camera, "cx", 0.0), getattr(camera, "cy", 0.0))
+        except AttributeError as e:
+            raise ValueError(f"camera: {e}") from None
+        if out is None:
+            out = RayView(torch.empty((1, H, W), dtype=torch.float32, device=self.device),
+                          torch.empty((3, H, W), dtype=torch.float32, device=self.device) if normals else None,
+                          torch.empty((3, H, W), dtype=torch.float32, device=self.device) if self.colors else None)
+        # the view's checks on the depth map that will be written: its size, its device, the camera's numbers
+        _, _, (M, c, _, cx_pix, cy_pix, fx, fy) = _check_view(self.device, out.depth, *cam, None, None, centre_from_view=True,
+                                                              normal=out.normal, rgb=out.rgb)
+        lib = L.load()
+        if skip is None:
+            skip = self.ray_skip()
+        table = skip.table if isinstance(skip, RaySkip) else None
+        ray = L.SfgsTsdfRay(L.C.sizeof(L.SfgsTsdfRay), H, W, M, c, cx_pix, cy_pix, fx, fy, near, far, step, out.depth.data_ptr(),
+                            None if out.normal is None else out.normal.data_ptr(), None if out.rgb is None else out.rgb.data_ptr())
+        vol = self._struct()
+        with torch.cuda.device(self.device):
+            L.check(lib.sfgs_tsdf_raycast(L.C.byref(vol), L.C.byref(ray), L.ptr(table), 0 if table is None else table.numel(),
+                                          _call.stream(self.device)))
+        return out
+
+
+class RaySkip:
+    """The result of TsdfVolume.ray_skip. table: uint8 [bz,by,bx] on the device, a byte per brick of 8 x 8 x 8 cells; dims: the
+    volume's dims it was made for."""
+
+    def __init__(self, table, dims):
+        self.table, self.dims = table, tuple(dims)
+
+
+class RayView:
+    """The result of TsdfVolume.raycast, on the device. depth: float32 [1,H,W], 0 where the ray found no surface; normal: float32
+    [3,H,W] in the world frame, unit length, toward the free side, zeros where depth is 0, or None; rgb: float32 [3,H,W], zeros
+    where depth is 0, or None when the volume keeps no colours. An ordinary view: depth goes into add_views, evaluate_dsm,
+    sfgs.pointcloud, sfgs.ortho and ViewSet as a rendered depth map does."""
+
+    def __init__(self, depth, normal, rgb):
+        self.depth, self.normal, self.rgb = depth, normal, rgb
 
 
 class TriangleSoup:
