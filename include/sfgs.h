@@ -24,6 +24,7 @@
  *   sfgs_ortho_*       (no counterpart: the script renders RGB per camera next to the depth, writes it to a PNG and keeps no georeferenced colour)   evaluate_gs_geometry.py:736-765
  *   sfgs_consistency_* (no counterpart: the script unprojects every rendered depth pixel it gets, evaluate_gs_geometry.py:767-776, and has no filter between the views)
  *   sfgs_tsdf_*        (no counterpart: the script has no mesh step; its geometry products are the DSM and the merged cloud, evaluate_gs_geometry.py:776-784)
+ *   sfgs_mesh_*        (no counterpart: the soup of sfgs_tsdf_extract welded into an indexed mesh, its components labelled, floaters removed)
  *   sfgs_raster_blend_stats, sfgs_blend_stats_views  (no counterpart: the reference's only pruning tool is GaussianModel.prune_by_radius, scene/gaussian_model.py:752, by distance)
  *   sfgs_similarity_transform  (no counterpart: the reference never merges scenes; it trains each in a frame of its own, scene/dataset_readers.py:378-390)
  *   sfgs_knn_dist2     simple_knn._C.distCUDA2(points)             scene/gaussian_model.py:25,324
@@ -928,6 +929,45 @@ typedef struct SfgsTsdfRay {
 size_t sfgs_tsdf_skip_bytes(int32_t nx, int32_t ny, int32_t nz);      /* 0: bad arguments (sfgs_last_error) */
 int sfgs_tsdf_skip_build(const SfgsTsdfVolume* vol, void* skip, size_t bytes, void* stream);
 int sfgs_tsdf_raycast(const SfgsTsdfVolume* vol, const SfgsTsdfRay* ray, const void* skip, size_t skip_bytes, void* stream);
+
+/* ---- Mesh: weld, components, clean (added under ABI 28: new symbols only; csrc/mesh.hip, csrc/mesh_math.h; Python: sfgs.mesh):
+ * the triangle soup finished on the device. Results are integers and copied bytes; tests/mesh_np.py states them in numpy and the
+ * kernels equal that restatement byte for byte, run after run. A `state` is four int64 words on the device, rewritten by every call:
+ * word 0 and 1 are counts (below), word 2 is a status (0: every loop ran to its end; bit 0 / 1 / 2: a probe, a find chain or a
+ * row of failed hooks reached its trip bound -- the slot count, m, 2^16 -- which valid input cannot; bit 3: a face index outside
+ * 0 ... m - 1 was met, its face skipped), word 3 is the weld's diagnostic.
+ * WELD, sfgs_mesh_weld. soup: float32 [n][3][3], the flat vertex index is q = 3 t + c; soup_colors: the same shape, or NULL.
+ *   key(q) is the three 32-bit words of soup[q] compared as BIT PATTERNS (-0.0 differs from +0.0, NaNs are equal when their bits are);
+ *   rep(q) = the smallest q' with key(q') == key(q); unique vertices are numbered in order of first appearance,
+ *   vid(q) = the number of representatives below rep(q). Outputs: vertices float32 [>= m][3] with vertices[vid] = soup[rep],
+ *   colors[vid] = soup_colors[rep] (given exactly when soup_colors is), faces int32 [n][3] with faces[t][c] = vid(3 t + c), state
+ *   word 0 = m, word 1 = n. m <= 3 n: buffers of 3 n rows always suffice. 0 <= n <= 2^29; n = 0 writes the state and launches nothing.
+ *   Mechanism: an open-addressing table of 32-bit slots holding soup vertex indices in `scratch` (the power of two >= 6 n slots),
+ *   linear probing, compare-and-swap into an empty slot, fetch-min on a slot whose witness has the same words; then the row
+ *   compaction below on the flags q == rep(q). flags: bit 0 = also sum the slots every insertion looked at into state word 3.
+ * VET, sfgs_mesh_vet: state of a caller's indexed mesh -- word 0 = m, word 1 = n, status bit 3 if a face index is out of range.
+ * COMPONENTS, sfgs_mesh_components. Vertices 0 ... m - 1, every face joins its three indices (degenerate faces too); labels int32
+ *   [m]: the smallest vertex index of the vertex's component (a vertex in no face is its own); per root r (labels[r] == r):
+ *   triangles[r] = the faces whose FIRST index lies in r's component, vertices_in[r] = its vertices; both int32 [m], zero elsewhere.
+ *   State word 0 = the number of components. Lock-free union-find on a parent array in `scratch`, larger root hooked under
+ *   the smaller; counts by integer atomics summed per wave and workgroup first. No float atomics.
+ * CLEAN, sfgs_mesh_clean. keep_root: one byte per vertex, read at roots only. A face is kept when keep_root[labels[faces[t][0]]]
+ *   is non-zero and (drop_degenerate == 0 or its three indices differ); a vertex is kept when a kept face references it. Both
+ *   compactions preserve order, faces are renumbered through the vertex ranks, colours travel with vertices. Outputs hold m / n
+ *   rows; state word 0 / 1 = the vertices / faces kept. Nothing is read back.
+ * Refusals are SFGS_E_ARG, made before any GPU work: a NULL pointer, n outside 0 ... 2^29, m outside 0 ... 2^31 - 1, faces over
+ * no vertex, colour pointers that do not come together, unknown flags, a scratch too small. No profiler ids of their own. */
+size_t sfgs_mesh_weld_scratch_bytes(int64_t n);                        /* 0: bad arguments (sfgs_last_error) */
+int sfgs_mesh_weld(const float* soup, const float* soup_colors, int64_t n, float* vertices, float* colors, int32_t* faces,
+                   long long* state, int32_t flags, void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_mesh_vet(const int32_t* faces, int64_t n, int64_t m, long long* state, void* stream);
+size_t sfgs_mesh_components_scratch_bytes(int64_t m);                  /* 0: bad arguments */
+int sfgs_mesh_components(const int32_t* faces, int64_t n, int64_t m, int32_t* labels, int32_t* triangles, int32_t* vertices_in,
+                         long long* state, void* scratch, size_t scratch_bytes, void* stream);
+size_t sfgs_mesh_clean_scratch_bytes(int64_t m, int64_t n);            /* 0: bad arguments */
+int sfgs_mesh_clean(const float* vertices, const float* colors, const int32_t* faces, int64_t m, int64_t n, const int32_t* labels,
+                    const unsigned char* keep_root, int32_t drop_degenerate, float* vertices_out, float* colors_out,
+                    int32_t* faces_out, long long* state, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the

@@ -8,27 +8,10 @@
 
 namespace sfgs {
 
-constexpr int CP_NT = 256, CP_ROWS_PER_THREAD = 16, CP_CHUNK = CP_NT * CP_ROWS_PER_THREAD;
 constexpr int CP_MAX_TENSORS = 48;
 constexpr int CP_WORDS_PER_THREAD = 8, CP_WORD_CHUNK = CP_NT * CP_WORDS_PER_THREAD;
 
-struct CompactScratch {
-  unsigned long long* total;  // [1] (+ padding)
-  unsigned* block_sum;        // [NB]
-  unsigned* dst_index;        // [N]
-};
-static inline int64_t cp_blocks(int64_t N) { return (N + CP_CHUNK - 1) / CP_CHUNK; }
-static inline size_t cp_scratch_bytes(int64_t N) {
-  return 256 + align_up((size_t)cp_blocks(N) * 4, 256) + align_up((size_t)N * 4, 256);
-}
-static inline CompactScratch cp_view(void* scratch, int64_t N) {
-  char* p = (char*)scratch;
-  CompactScratch s;
-  s.total = (unsigned long long*)p; p += 256;
-  s.block_sum = (unsigned*)p; p += align_up((size_t)cp_blocks(N) * 4, 256);
-  s.dst_index = (unsigned*)p;
-  return s;
-}
+// CompactScratch / cp_blocks / cp_scratch_bytes / cp_view: sfgs_internal.h (mesh.hip reads a plan's ranks too)
 
 __global__ void __launch_bounds__(CP_NT)
 compact_count_kernel(const unsigned char* __restrict__ keep, long long N, unsigned* __restrict__ block_sum) {

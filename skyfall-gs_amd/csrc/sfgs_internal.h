@@ -604,6 +604,26 @@ __device__ __forceinline__ unsigned block_excl_scan_u32(unsigned v, unsigned* to
   return res;
 }
 
+// ---- the row compaction's scratch (compact.hip: sfgs_compact_plan writes it, sfgs_compact_rows and mesh.hip read it) ------------
+constexpr int CP_NT = 256, CP_ROWS_PER_THREAD = 16, CP_CHUNK = CP_NT * CP_ROWS_PER_THREAD;
+struct CompactScratch {
+  unsigned long long* total;  // [1] (+ padding)
+  unsigned* block_sum;        // [NB]
+  unsigned* dst_index;        // [N]
+};
+static inline int64_t cp_blocks(int64_t N) { return (N + CP_CHUNK - 1) / CP_CHUNK; }
+static inline size_t cp_scratch_bytes(int64_t N) {
+  return 256 + align_up((size_t)cp_blocks(N) * 4, 256) + align_up((size_t)N * 4, 256);
+}
+static inline CompactScratch cp_view(void* scratch, int64_t N) {
+  char* p = (char*)scratch;
+  CompactScratch s;
+  s.total = (unsigned long long*)p; p += 256;
+  s.block_sum = (unsigned*)p; p += align_up((size_t)cp_blocks(N) * 4, 256);
+  s.dst_index = (unsigned*)p;
+  return s;
+}
+
 // ---- the forward's stages: a translation unit each, every kernel launched from the file that defines it. The entry
 // points of raster_fwd.hip validate, build the views and call these in stream order; each returns an SFGS_* code.
 int check_frame(const SfgsFrame* f);                               // raster_fwd.hip

@@ -264,6 +264,13 @@ SYMBOLS = {
     "sfgs_tsdf_skip_bytes": (_SZ, [_I32, _I32, _I32]),
     "sfgs_tsdf_skip_build": (C.c_int, [C.POINTER(SfgsTsdfVolume), _V, _SZ, _V]),
     "sfgs_tsdf_raycast": (C.c_int, [C.POINTER(SfgsTsdfVolume), C.POINTER(SfgsTsdfRay), _V, _SZ, _V]),
+    "sfgs_mesh_weld_scratch_bytes": (_SZ, [_I64]),
+    "sfgs_mesh_weld": (C.c_int, [_V, _V, _I64, _V, _V, _V, _V, _I32, _V, _SZ, _V]),
+    "sfgs_mesh_vet": (C.c_int, [_V, _I64, _I64, _V, _V]),
+    "sfgs_mesh_components_scratch_bytes": (_SZ, [_I64]),
+    "sfgs_mesh_components": (C.c_int, [_V, _I64, _I64, _V, _V, _V, _V, _V, _SZ, _V]),
+    "sfgs_mesh_clean_scratch_bytes": (_SZ, [_I64, _I64]),
+    "sfgs_mesh_clean": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _V, _I32, _V, _V, _V, _V, _V, _SZ, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

@@ -1,0 +1,261 @@
+"""sfgs.mesh -- the triangle soup of sfgs.tsdf finished on the device (csrc/mesh.hip through libsfgs.so): welded into an indexed
+mesh, its connected components labelled and counted, floaters and degenerate faces removed. The reference has no mesh step.
+
+    soup = vol.extract(capacity=8_000_000)                             # sfgs.tsdf
+    mesh = soup.mesh()                                                 # weld: V [m,3], F [n,3] int32, colours; nothing read back
+    cc = mesh.components()                                             # labels [m], triangles [m], vertices_in [m], count
+    clean = mesh.clean(min_triangles=64, largest=1)                    # a new Mesh; drop_degenerate=True drops zero-area faces
+    clean.save_ply("city.ply", origin=(utm_x, utm_y, alt))
+
+Weld (include/sfgs.h states it in full, tests/mesh_np.py in numpy; the kernels equal that restatement byte for byte): two soup
+vertices are one when their twelve bytes are equal (-0.0 is not +0.0, NaNs are equal when their bits are); the unique vertices
+are numbered in order of first appearance and take the colour of that first appearance. Sorting V by its bytes gives
+TriangleSoup.weld()'s V. Components: every face joins its three indices, a label is the smallest vertex index of the component,
+`triangles` counts the faces by their first index (degenerate faces too). Clean keeps a component when it has at least
+min_triangles faces and is among the first `largest` ordered by (triangles descending, label ascending); a face when its
+component is kept and, with drop_degenerate, its three indices differ; a vertex when a kept face references it. Order is preserved.
+
+A Mesh's buffers are sized for the worst case and its counts live on the device; the sized views (vertices, faces, colors) cost
+ONE host read per Mesh, on first use, which also reports a status the kernels left (an index out of range, a loop bound reached).
+components() and clean() need their input's sizes and so count as such a use; what they return is read back only when asked.
+
+There is no vertex normal, decimation, hole filling or smoothing, and no torch fallback: without the HIP library every operator raises."""
+import os
+
+import numpy as np
+import torch
+
+from . import _call
+from . import _lib as L
+from .geometry import _vec
+
+__all__ = ["Mesh", "Components", "weld", "MAX_TRIANGLES"]
+
+MAX_TRIANGLES = 1 << 29
+_INT32_MAX = int(np.iinfo(np.int32).max)
+_ST_BOUND, _ST_BAD_INDEX = 7, 8
+
+
+def _raise_status(status, what):
+    if status & _ST_BAD_INDEX:
+        raise ValueError(f"{what}: a face index lies outside 0 ... num_vertices - 1 (the face was skipped, nothing was indexed)")
+    if status & _ST_BOUND:
+        raise RuntimeError(f"{what}: a probe / find / retry loop reached its trip bound (status {status}); the result is not valid")
+
+
+def _device_of(t):
+    return t.device if t.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def weld(vertices, colors=None, num_triangles=None, probe_stats=False):
+    """-> Mesh. vertices: float32 [n,3,3] on the GPU, contiguous (a triangle soup); colors: None or the same shape;
+    num_triangles: weld the first so many rows only (default: all). probe_stats: also sum the table slots every insertion
+    looked at (Mesh.weld_probes; a diagnostic of tools/bench_mesh.py, it costs an atomic per wave)."""
+    _call.check_tensor("vertices", vertices, "[n,3,3]", lambda t: t.dim() == 3 and tuple(t.shape[1:]) == (3, 3))
+    _call.check_tensor("colors", colors, f"{tuple(vertices.shape)}", lambda t: t.shape == vertices.shape, none_ok=True)
+    rows = int(vertices.shape[0])
+    if num_triangles is None:
+        num_triangles = rows
+    if isinstance(num_triangles, bool) or not isinstance(num_triangles, (int, np.integer)) or not 0 <= num_triangles <= rows:
+        raise ValueError(f"num_triangles must be an integer in 0 ... {rows}, got {num_triangles!r}")
+    n = int(num_triangles)
+    if n > MAX_TRIANGLES:
+        raise ValueError(f"at most 2^29 triangles, got {n}")
+    _call.check_gpu(vertices=vertices, colors=colors)
+    dev = _device_of(vertices)
+    _call.same_device(dev, "vertices' device", colors=colors)
+    if not vertices.is_contiguous() or (colors is not None and not colors.is_contiguous()):
+        raise ValueError("vertices and colors must be contiguous")
+    lib = L.load()
+    V = torch.empty((3 * n, 3), dtype=torch.float32, device=dev)
+    Cc = None if colors is None else torch.empty((3 * n, 3), dtype=torch.float32, device=dev)
+    F = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    state = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        scratch = _call.scratch(lib.sfgs_mesh_weld_scratch_bytes(n), dev, refused_if_zero=n > 0)
+        L.check(lib.sfgs_mesh_weld(L.ptr(vertices.detach()), L.ptr(None if colors is None else colors.detach()), n, L.ptr(V), L.ptr(Cc),
+                                   L.ptr(F), L.ptr(state), int(bool(probe_stats)), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+    return Mesh._made(V, F, Cc, state, "weld")
+
+
+class Components:
+    """The result of Mesh.components, on the device. labels int32 [m]: the smallest vertex index of the vertex's component;
+    triangles / vertices_in int32 [m]: per root (labels[r] == r) the faces whose first index lies in the component and its
+    vertices, zero elsewhere; count: int64 [] the number of components."""
+
+    def __init__(self, labels, triangles, vertices_in, state):
+        self.labels, self.triangles, self.vertices_in, self._state = labels, triangles, vertices_in, state
+
+    @property
+    def count(self):
+        return self._state[0]
+
+    def check(self):
+        """ONE host read: raises if the kernels left a status; -> the number of components as an int."""
+        count, _, status, _ = self._state.tolist()
+        _raise_status(status, "components")
+        return count
+
+
+class Mesh:
+    """An indexed triangle mesh on the device. Mesh(vertices, faces, colors=None) takes a caller's mesh: vertices float32 [m,3],
+    faces int32 [n,3], colors None or float32 [m,3], all contiguous on one GPU; the face indices are vetted on the device and a
+    bad one is reported by the first use of a sized view, components() or clean().
+    vertex_buffer / face_buffer / color_buffer: the storage, rows at or beyond the counts never written."""
+
+    def __init__(self, vertices, faces, colors=None):
+        _call.check_tensor("vertices", vertices, "[m,3]", lambda t: t.dim() == 2 and t.shape[1] == 3)
+        _call.check_tensor("faces", faces, "[n,3]", lambda t: t.dim() == 2 and t.shape[1] == 3, dtypes=(torch.int32,))
+        _call.check_tensor("colors", colors, f"{tuple(vertices.shape)}", lambda t: t.shape == vertices.shape, none_ok=True)
+        m, n = int(vertices.shape[0]), int(faces.shape[0])
+        if m > _INT32_MAX or n > MAX_TRIANGLES:
+            raise ValueError(f"at most 2^31 - 1 vertices and 2^29 faces, got {m} and {n}")
+        if n > 0 and m == 0:
+            raise ValueError(f"{n} faces over no vertex")
+        _call.check_gpu(vertices=vertices, faces=faces, colors=colors)
+        dev = _device_of(vertices)
+        _call.same_device(dev, "vertices' device", faces=faces, colors=colors)
+        if not (vertices.is_contiguous() and faces.is_contiguous() and (colors is None or colors.is_contiguous())):
+            raise ValueError("vertices, faces and colors must be contiguous")
+        lib = L.load()
+        state = torch.empty(4, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.sfgs_mesh_vet(L.ptr(faces), n, m, L.ptr(state), _call.stream(dev)))
+        self._set(vertices.detach(), faces, None if colors is None else colors.detach(), state, "Mesh")
+
+    def _set(self, V, F, Cc, state, what):
+        self.vertex_buffer, self.face_buffer, self.color_buffer, self._state, self._what = V, F, Cc, state, what
+        self._sizes_read = None
+        self.device = V.device
+
+    @classmethod
+    def _made(cls, V, F, Cc, state, what):
+        self = cls.__new__(cls)
+        self._set(V, F, Cc, state, what)
+        return self
+
+    @property
+    def num_vertices(self):
+        """int64 [] on the device"""
+        return self._state[0]
+
+    @property
+    def num_faces(self):
+        """int64 [] on the device"""
+        return self._state[1]
+
+    def _sizes(self):
+        if self._sizes_read is None:                      # ONE host read
+            m, n, status, aux = self._state.tolist()
+            _raise_status(status, self._what)
+            assert 0 <= m <= self.vertex_buffer.shape[0] and 0 <= n <= self.face_buffer.shape[0], (m, n)
+            self._sizes_read, self._aux = (m, n), aux
+        return self._sizes_read
+
+    @property
+    def weld_probes(self):
+        """The table slots the weld's insertions looked at in all (weld(..., probe_stats=True)), an int; 0 otherwise."""
+        self._sizes()
+        return self._aux
+
+    @property
+    def vertices(self):
+        """float32 [m,3] on the device: a view of the valid rows"""
+        return self.vertex_buffer[:self._sizes()[0]]
+
+    @property
+    def faces(self):
+        """int32 [n,3] on the device"""
+        return self.face_buffer[:self._sizes()[1]]
+
+    @property
+    def colors(self):
+        """float32 [m,3] on the device, or None"""
+        return None if self.color_buffer is None else self.color_buffer[:self._sizes()[0]]
+
+    def components(self):
+        """-> Components. Four launches, nothing read back beyond this mesh's own sizes."""
+        m, n = self._sizes()
+        dev, lib = self.device, L.load()
+        labels, triangles, vertices_in = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
+        state = torch.empty(4, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            scratch = _call.scratch(lib.sfgs_mesh_components_scratch_bytes(m), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_components(L.ptr(self.face_buffer), n, m, L.ptr(labels), L.ptr(triangles), L.ptr(vertices_in),
+                                             L.ptr(state), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+        return Components(labels, triangles, vertices_in, state)
+
+    def clean(self, min_triangles=None, largest=None, drop_degenerate=False, components=None):
+        """-> a new Mesh with the components below min_triangles faces and those beyond the first `largest` (by triangles
+        descending, label ascending) removed, with drop_degenerate also the faces with two equal indices, and then every vertex
+        that no kept face references. components: a components() result of THIS mesh, to save recomputing it; labels are not
+        recomputed after faces were dropped. Outputs have this mesh's sizes; a clean that keeps everything equals its input."""
+        for name, v in (("min_triangles", min_triangles), ("largest", largest)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0):
+                raise ValueError(f"{name} must be None or a non-negative integer, got {v!r}")
+        if not isinstance(drop_degenerate, (bool, np.bool_)):
+            raise ValueError(f"drop_degenerate must be a bool, got {drop_degenerate!r}")
+        if components is not None and not isinstance(components, Components):
+            raise ValueError(f"components must be a components() result, got {components!r}")
+        m, n = self._sizes()
+        if components is not None and (components.labels.shape[0] != m or components.labels.device != self.device):
+            raise ValueError("components were made for another mesh")
+        dev, lib = self.device, L.load()
+        cc = self.components() if components is None else components
+        with torch.cuda.device(dev):
+            # the component rule, on the device: plumbing over m integers, no host read
+            is_root = cc.labels == torch.arange(m, dtype=torch.int32, device=dev)
+            keep_root = is_root.clone()
+            if min_triangles is not None:
+                keep_root &= cc.triangles >= int(min(min_triangles, _INT32_MAX))
+            if largest is not None:
+                key = torch.where(is_root, -cc.triangles.to(torch.int64), torch.ones((), dtype=torch.int64, device=dev))
+                order = torch.sort(key, stable=True).indices[:min(int(largest), m)]          # roots first, ties by ascending label
+                top = torch.zeros(m, dtype=torch.bool, device=dev)
+                top[order] = True
+                keep_root &= top
+            keep_root = keep_root.to(torch.uint8)
+            V = torch.empty((m, 3), dtype=torch.float32, device=dev)
+            Cc = None if self.color_buffer is None else torch.empty((m, 3), dtype=torch.float32, device=dev)
+            F = torch.empty((n, 3), dtype=torch.int32, device=dev)
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            scratch = _call.scratch(lib.sfgs_mesh_clean_scratch_bytes(m, n), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_clean(L.ptr(self.vertex_buffer), L.ptr(self.color_buffer), L.ptr(self.face_buffer), m, n,
+                                        L.ptr(cc.labels), L.ptr(keep_root), int(bool(drop_degenerate)), L.ptr(V), L.ptr(Cc), L.ptr(F),
+                                        L.ptr(state), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+        return Mesh._made(V, F, Cc, state, "clean")
+
+    def save_ply(self, path, origin=None):
+        """Binary little-endian PLY in TriangleSoup.save_ply's layout: a `vertex` and a `face` element (`property list uchar int
+        vertex_indices`), vertices `double` with origin (added in float64) and `float` without, with colours `uchar red / green /
+        blue` by (x * 255 + 0.5).clip(0, 255), NaN -> 0."""
+        org = None if origin is None else _vec(origin, 3, "origin")
+        V = np.ascontiguousarray(self.vertices.cpu().numpy())
+        F = np.ascontiguousarray(self.faces.cpu().numpy())
+        if len(V) > _INT32_MAX:
+            raise ValueError(f"{len(V)} vertices do not fit the PLY's int indices")
+        kind, ftype = ("double", "<f8") if org is not None else ("float", "<f4")
+        fields = [(a, ftype) for a in "xyz"]
+        header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(V)}"] + [f"property {kind} {a}" for a in "xyz"]
+        if self.color_buffer is not None:
+            fields += [(c, "u1") for c in ("red", "green", "blue")]
+            header += [f"property uchar {c}" for c in ("red", "green", "blue")]
+        header += [f"element face {len(F)}", "property list uchar int vertex_indices", "end_header"]
+        vt = np.empty(len(V), dtype=fields)
+        for j, a in enumerate("xyz"):
+            vt[a] = V[:, j] if org is None else V[:, j].astype(np.float64) + org[j]
+        if self.color_buffer is not None:
+            c = np.ascontiguousarray(self.colors.cpu().numpy())
+            with np.errstate(invalid="ignore"):
+                q = np.where(np.isnan(c), np.float32(0), (c * np.float32(255) + np.float32(0.5)).clip(0, 255)).astype(np.uint8)
+            for j, name in enumerate(("red", "green", "blue")):
+                vt[name] = q[:, j]
+        ft = np.empty(len(F), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        ft["n"], ft["i"] = 3, F
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(("\n".join(header) + "\n").encode("ascii"))
+            vt.tofile(f)
+            ft.tofile(f)

@@ -7,6 +7,7 @@ is unconnected points; this is the surface. The reference has no mesh step.
     vol.add_views(depths, cameras, masks=vs.masks(), images=images)    # one launch per batch of <= 256 views
     soup = vol.extract(capacity=8_000_000)                             # three launches, nothing read back
     soup.save_ply("city.ply", origin=(utm_x, utm_y, alt))              # welded, binary, double vertices
+    mesh = soup.mesh()                                                 # sfgs.mesh: welded on the device, to label and clean there
 
 The volume is axis-aligned in the cameras' own frame; voxel (i, j, k) has its centre at origin + (i + 0.5, j + 0.5, k + 0.5) *
 voxel_size. Integration (include/sfgs.h states it in full, tests/tsdf_np.py in numpy; the kernel equals that restatement byte
@@ -354,6 +355,12 @@ class TriangleSoup:
         bytes: V is in byte order). Every tetrahedron that shares an edge produced the same bytes for its point."""
         V, F, _ = self._welded()
         return V, F
+
+    def mesh(self):
+        """On the device -> sfgs.mesh.Mesh: the welded, indexed mesh (vertices in order of first appearance, int32 faces, the
+        colour of a vertex's first appearance), to label and clean there. ValueError when more triangles were found than stored."""
+        from . import mesh as _mesh
+        return _mesh.weld(self.buffer, self.color_buffer, self._valid())
 
     def save_ply(self, path, weld=True, origin=None):
         """Binary little-endian PLY with a `vertex` and a `face` element (`property list uchar int vertex_indices`). Vertices
