@@ -969,6 +969,54 @@ int sfgs_mesh_clean(const float* vertices, const float* colors, const int32_t* f
                     const unsigned char* keep_root, int32_t drop_degenerate, float* vertices_out, float* colors_out,
                     int32_t* faces_out, long long* state, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Mesh: decimation, vertex -> face adjacency, vertex normals (added under ABI 28: new symbols only; csrc/mesh.hip,
+ * csrc/mesh_math.h; Python: Mesh.decimate / vertex_faces / vertex_normals). tests/mesh_simplify_np.py states the results in numpy
+ * from these definitions and the kernels equal it byte for byte, run after run. `state` as above; two more meanings of its status:
+ * bit 1 is also raised when the adjacency's segment sort reaches its trip bound, bit 4 (16) when the decimation met a BAD vertex.
+ * All float64 arithmetic below is one rounded operation at a time (no fused multiply-add).
+ * DECIMATE, sfgs_mesh_decimate: vertex clustering on the grid of `cell` (finite, > 0) at `origin` (finite). m vertices, n faces.
+ *   1. Cell of vertex v, per axis a: u = (float64(V[v][a]) - origin[a]) / cell (a division), i = floor(u), f = u - i (0 <= f <= 1;
+ *      1 only when a tiny negative u rounds), p = uint64(floor(f * 2^32)). v is BAD when some u is not finite or some i lies
+ *      outside int32: it joins no cluster, every face that names it is dropped, status bit 4 is raised.
+ *   2. Vertices with the same three int32 cell indices form a cluster; clusters are numbered in order of first appearance (by
+ *      their smallest member). All m vertices take part, referenced by a face or not.
+ *   3. Cluster vertex: c = the member count, S[a] = the sum of p in uint64 (<= 2^31 * 2^32);
+ *      P[a] = float32((float64(i[a]) + float64(S[a] / c) * 2^-32) * cell + origin[a]), the division an integer division.
+ *      Colours: x = the member's component, NaN -> 0, clamped to [0, 1] in float64, Sc = the sum of uint64(floor(x * 2^32)),
+ *      colour = float32(float64(Sc / c) * 2^-32). A cluster with ONE member copies that member's position and colour bytes.
+ *   4. Faces: G[t] = cluster_of[F[t]]. A face is dropped when an index is out of range (status bit 3) or names a bad vertex, when
+ *      two of its new indices are equal, or -- flags bit 0, drop_duplicates -- when an earlier face that was not dropped for the
+ *      reasons before has the same SET of three new indices: of such faces the smallest t stays, with its own winding.
+ *   5. A cluster is kept when a kept face references it. Both compactions preserve order; faces are renumbered through the
+ *      cluster ranks. Outputs hold m / n rows; state word 0 / 1 = the vertices / faces kept; vertex_map (or NULL): int32 [m], the
+ *      output index of each input vertex's cluster, -1 when that cluster was dropped or the vertex was bad.
+ *   flags bit 1: also sum the table slots the cluster insertions looked at into state word 3 (0 otherwise).
+ *   Mechanism: the weld's table over the twelve-byte cell keys (the power of two >= 2 m slots), the row compaction's plan for the
+ *   first-appearance ranks, relaxed agent-scope integer atomics for the count and the 64-bit sums, the same table again over the
+ *   sorted triples of the faces (>= 2 n slots), the clean's compactions. Nothing depends on the order of arrival.
+ * VERTEX_FACES, sfgs_mesh_vertex_faces: the inverted index. The flat corner record of face t, corner c is r = 3 t + c. offsets
+ *   int32 [m + 1], records int32 [3 n]: records[offsets[v] ... offsets[v + 1]) holds every r with F[t][c] == v, ASCENDING
+ *   (a stable argsort of the flattened faces, and the cumulative counts); a face that names v twice appears twice. A corner
+ *   whose index is out of range is left out (status bit 3). State word 0 / 1 = m / n. Mechanism: integer-atomic counts, an
+ *   exclusive scan, a fill through atomic cursors, then a thread per vertex sorts its own segment (insertion sort up to 32
+ *   records, heapsort beyond, trip bound 2 k (log2 k + 2)).
+ * VERTEX_NORMALS, sfgs_mesh_vertex_normals: normals float32 [m][3]. Face normal in float64 from the float32 positions a, b, c of
+ *   F[t]: e1 = b - a, e2 = c - a, n_t = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x) (area-weighted, winding as
+ *   stored). N_v = the sum of n_(r / 3) over v's records in ascending r, from +0.0, in float64; len = sqrt((Nx Nx + Ny Ny) + Nz Nz);
+ *   the output is float32(N / len) per component when len > 0 and finite, else (0, 0, 0). One thread per vertex walks its
+ *   segment: no atomics. offsets / records: a vertex_faces result of the same mesh. `state` is NOT reset: status bits are added.
+ * Refusals are SFGS_E_ARG, made before any GPU work: a NULL pointer, sizes out of range, faces over no vertex, a cell that is not
+ * finite and positive, an origin that is not finite, colour pointers that do not come together, unknown flags, a scratch too small. */
+size_t sfgs_mesh_decimate_scratch_bytes(int64_t m, int64_t n, int32_t with_colors);      /* 0: bad arguments */
+int sfgs_mesh_decimate(const float* vertices, const float* colors, const int32_t* faces, int64_t m, int64_t n, double cell,
+                       double origin_x, double origin_y, double origin_z, int32_t flags, float* vertices_out, float* colors_out,
+                       int32_t* faces_out, int32_t* vertex_map, long long* state, void* scratch, size_t scratch_bytes, void* stream);
+size_t sfgs_mesh_vertex_faces_scratch_bytes(int64_t m);                /* 0: bad arguments */
+int sfgs_mesh_vertex_faces(const int32_t* faces, int64_t n, int64_t m, int32_t* offsets, int32_t* records, long long* state,
+                           void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t m, int64_t n, const int32_t* offsets,
+                             const int32_t* records, float* normals, long long* state, void* stream);
+
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the
  * per-pixel tests, before the pixel saturated -- with blend weight w = alpha T:

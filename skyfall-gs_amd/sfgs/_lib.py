@@ -271,6 +271,12 @@ SYMBOLS = {
     "sfgs_mesh_components": (C.c_int, [_V, _I64, _I64, _V, _V, _V, _V, _V, _SZ, _V]),
     "sfgs_mesh_clean_scratch_bytes": (_SZ, [_I64, _I64]),
     "sfgs_mesh_clean": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _V, _I32, _V, _V, _V, _V, _V, _SZ, _V]),
+    "sfgs_mesh_decimate_scratch_bytes": (_SZ, [_I64, _I64, _I32]),
+    "sfgs_mesh_decimate": (C.c_int, [_V, _V, _V, _I64, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I32, _V, _V, _V, _V, _V,
+                                     _V, _SZ, _V]),
+    "sfgs_mesh_vertex_faces_scratch_bytes": (_SZ, [_I64]),
+    "sfgs_mesh_vertex_faces": (C.c_int, [_V, _I64, _I64, _V, _V, _V, _V, _SZ, _V]),
+    "sfgs_mesh_vertex_normals": (C.c_int, [_V, _V, _I64, _I64, _V, _V, _V, _V, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

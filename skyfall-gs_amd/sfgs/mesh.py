@@ -19,7 +19,20 @@ A Mesh's buffers are sized for the worst case and its counts live on the device;
 ONE host read per Mesh, on first use, which also reports a status the kernels left (an index out of range, a loop bound reached).
 components() and clean() need their input's sizes and so count as such a use; what they return is read back only when asked.
 
-There is no vertex normal, decimation, hole filling or smoothing, and no torch fallback: without the HIP library every operator raises."""
+Decimate, adjacency, normals (include/sfgs.h in words, tests/mesh_simplify_np.py in numpy; byte for byte as well):
+
+    small = clean.decimate(cell=2 * voxel, origin=vol_origin)          # vertex clustering: a new Mesh at most as large
+    adj = small.vertex_faces()                                         # (offsets [m+1], records [3n]): corner records 3t+c per vertex
+    normals = small.vertex_normals(adjacency=adj)                      # float32 [m,3], area-weighted, summed in a fixed order
+    small.save_ply("city_small.ply", origin=(utm_x, utm_y, alt), normals=normals)
+
+decimate puts every vertex into the cell floor((x - origin) / cell) of a grid, replaces each cell's vertices by their mean (an
+integer mean of 32-bit fixed-point offsets inside the cell, so it does not depend on the order of summation; a cell with one
+vertex keeps that vertex's bytes), maps the faces through the cells and drops those that collapse, those that repeat an earlier
+face's set of three vertices (drop_duplicates) and then every cell no face is left on. A vertex whose cell is not finite or
+leaves int32 is bad: it joins no cell, its faces go, and the result's first sized use raises ValueError.
+
+There is no hole filling or smoothing, and no torch fallback: without the HIP library every operator raises."""
 import os
 
 import numpy as np
@@ -29,14 +42,16 @@ from . import _call
 from . import _lib as L
 from .geometry import _vec
 
-__all__ = ["Mesh", "Components", "weld", "MAX_TRIANGLES"]
+__all__ = ["Mesh", "Components", "VertexFaces", "weld", "MAX_TRIANGLES"]
 
 MAX_TRIANGLES = 1 << 29
 _INT32_MAX = int(np.iinfo(np.int32).max)
-_ST_BOUND, _ST_BAD_INDEX = 7, 8
+_ST_BOUND, _ST_BAD_INDEX, _ST_BAD_VERTEX = 7, 8, 16
 
 
 def _raise_status(status, what):
+    if status & _ST_BAD_VERTEX:
+        raise ValueError(f"{what}: a vertex is not finite or its cell index leaves int32 (it joined no cluster, its faces were dropped)")
     if status & _ST_BAD_INDEX:
         raise ValueError(f"{what}: a face index lies outside 0 ... num_vertices - 1 (the face was skipped, nothing was indexed)")
     if status & _ST_BOUND:
@@ -97,6 +112,22 @@ class Components:
         return count
 
 
+class VertexFaces(tuple):
+    """The result of Mesh.vertex_faces, on the device: the tuple (offsets int32 [m+1], records int32 [3n]). Vertex v's segment
+    records[offsets[v]:offsets[v+1]] holds the corner records r = 3 t + c with faces[t][c] == v, ascending."""
+
+    def __new__(cls, offsets, records, state):
+        self = super().__new__(cls, (offsets, records))
+        self.offsets, self.records, self._state = offsets, records, state
+        return self
+
+    def check(self):
+        """ONE host read: raises if the kernels left a status (vertex_normals adds its own to it); -> the status, 0."""
+        status = int(self._state[2])
+        _raise_status(status, "vertex_faces")
+        return status
+
+
 class Mesh:
     """An indexed triangle mesh on the device. Mesh(vertices, faces, colors=None) takes a caller's mesh: vertices float32 [m,3],
     faces int32 [n,3], colors None or float32 [m,3], all contiguous on one GPU; the face indices are vetted on the device and a
@@ -154,7 +185,8 @@ class Mesh:
 
     @property
     def weld_probes(self):
-        """The table slots the weld's insertions looked at in all (weld(..., probe_stats=True)), an int; 0 otherwise."""
+        """The table slots the weld's insertions looked at in all (weld(..., probe_stats=True); for a decimated mesh the cluster
+        insertions of decimate(..., probe_stats=True)), an int; 0 otherwise."""
         self._sizes()
         return self._aux
 
@@ -225,18 +257,89 @@ class Mesh:
                                         L.ptr(state), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
         return Mesh._made(V, F, Cc, state, "clean")
 
-    def save_ply(self, path, origin=None):
+    def decimate(self, cell, origin=(0.0, 0.0, 0.0), drop_duplicates=True, return_map=False, probe_stats=False):
+        """-> a new Mesh (with return_map: (Mesh, int32 [m] on the device: the output index of each input vertex's cluster, -1
+        when it was dropped or the vertex was bad)) by vertex clustering on the grid of `cell` at `origin`; the module's docstring
+        and include/sfgs.h state the result. Outputs have this mesh's sizes; nothing is read back beyond this mesh's own sizes.
+        probe_stats: also sum the table slots the cluster insertions looked at (the result's weld_probes; a diagnostic)."""
+        if isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating)) or not np.isfinite(cell) or cell <= 0:
+            raise ValueError(f"cell must be a finite number > 0, got {cell!r}")
+        org = _vec(origin, 3, "origin")
+        if not np.isfinite(org).all():
+            raise ValueError(f"origin must be finite, got {origin!r}")
+        for name, v in (("drop_duplicates", drop_duplicates), ("return_map", return_map), ("probe_stats", probe_stats)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{name} must be a bool, got {v!r}")
+        m, n = self._sizes()
+        dev, lib = self.device, L.load()
+        with torch.cuda.device(dev):
+            V = torch.empty((m, 3), dtype=torch.float32, device=dev)
+            Cc = None if self.color_buffer is None else torch.empty((m, 3), dtype=torch.float32, device=dev)
+            F = torch.empty((n, 3), dtype=torch.int32, device=dev)
+            vmap = torch.empty(m, dtype=torch.int32, device=dev) if return_map else None
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            scratch = _call.scratch(lib.sfgs_mesh_decimate_scratch_bytes(m, n, int(Cc is not None)), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_decimate(L.ptr(self.vertex_buffer), L.ptr(self.color_buffer), L.ptr(self.face_buffer), m, n, float(cell),
+                                           float(org[0]), float(org[1]), float(org[2]), int(bool(drop_duplicates)) | 2 * int(bool(probe_stats)),
+                                           L.ptr(V), L.ptr(Cc), L.ptr(F), L.ptr(vmap), L.ptr(state), L.ptr(scratch), scratch.numel(),
+                                           _call.stream(dev)))
+        out = Mesh._made(V, F, Cc, state, "decimate")
+        return (out, vmap) if return_map else out
+
+    def vertex_faces(self):
+        """-> VertexFaces, the tuple (offsets int32 [m+1], records int32 [3n]) on the device: the vertex -> face inverted index
+        over the corner records r = 3 t + c, every segment ascending (np.argsort(F.reshape(-1), kind="stable") and the
+        cumulative counts). A face that names a vertex twice appears twice in its segment."""
+        m, n = self._sizes()
+        dev, lib = self.device, L.load()
+        with torch.cuda.device(dev):
+            offsets = torch.empty(m + 1, dtype=torch.int32, device=dev)
+            records = torch.empty(3 * n, dtype=torch.int32, device=dev)
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            scratch = _call.scratch(lib.sfgs_mesh_vertex_faces_scratch_bytes(m), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_vertex_faces(L.ptr(self.face_buffer), n, m, L.ptr(offsets), L.ptr(records), L.ptr(state), L.ptr(scratch),
+                                               scratch.numel(), _call.stream(dev)))
+        return VertexFaces(offsets, records, state)
+
+    def vertex_normals(self, adjacency=None):
+        """-> float32 [m,3] on the device: per vertex the float64 sum of its faces' area-weighted normals (b - a) x (c - a), taken
+        in ascending order of the corner records and normalised; (0, 0, 0) where the sum has no finite positive length.
+        adjacency: a vertex_faces() result of THIS mesh, to save rebuilding it."""
+        if adjacency is not None and not isinstance(adjacency, VertexFaces):
+            raise ValueError(f"adjacency must be a vertex_faces() result, got {adjacency!r}")
+        m, n = self._sizes()
+        if adjacency is not None and (adjacency.offsets.shape[0] != m + 1 or adjacency.records.shape[0] != 3 * n or
+                                      adjacency.offsets.device != self.device):
+            raise ValueError("adjacency was made for another mesh")
+        adj = self.vertex_faces() if adjacency is None else adjacency
+        dev, lib = self.device, L.load()
+        with torch.cuda.device(dev):
+            normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
+            L.check(lib.sfgs_mesh_vertex_normals(L.ptr(self.vertex_buffer), L.ptr(self.face_buffer), m, n, L.ptr(adj.offsets),
+                                                 L.ptr(adj.records), L.ptr(normals), L.ptr(adj._state), _call.stream(dev)))
+        return normals
+
+    def save_ply(self, path, origin=None, normals=None):
         """Binary little-endian PLY in TriangleSoup.save_ply's layout: a `vertex` and a `face` element (`property list uchar int
         vertex_indices`), vertices `double` with origin (added in float64) and `float` without, with colours `uchar red / green /
-        blue` by (x * 255 + 0.5).clip(0, 255), NaN -> 0."""
+        blue` by (x * 255 + 0.5).clip(0, 255), NaN -> 0. normals: float32 [m,3] on the mesh's device (vertex_normals()); they
+        go in as `float nx / ny / nz` after z and before the colours."""
         org = None if origin is None else _vec(origin, 3, "origin")
         V = np.ascontiguousarray(self.vertices.cpu().numpy())
+        if normals is not None:
+            if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (len(V), 3):
+                raise ValueError(f"normals must be a float32 tensor of shape ({len(V)}, 3)")
+            if normals.device != self.vertex_buffer.device:
+                raise ValueError(f"normals must be on the mesh's device {self.vertex_buffer.device}, got {normals.device}")
         F = np.ascontiguousarray(self.faces.cpu().numpy())
         if len(V) > _INT32_MAX:
             raise ValueError(f"{len(V)} vertices do not fit the PLY's int indices")
         kind, ftype = ("double", "<f8") if org is not None else ("float", "<f4")
         fields = [(a, ftype) for a in "xyz"]
         header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(V)}"] + [f"property {kind} {a}" for a in "xyz"]
+        if normals is not None:
+            fields += [(a, "<f4") for a in ("nx", "ny", "nz")]
+            header += [f"property float {a}" for a in ("nx", "ny", "nz")]
         if self.color_buffer is not None:
             fields += [(c, "u1") for c in ("red", "green", "blue")]
             header += [f"property uchar {c}" for c in ("red", "green", "blue")]
@@ -244,6 +347,10 @@ class Mesh:
         vt = np.empty(len(V), dtype=fields)
         for j, a in enumerate("xyz"):
             vt[a] = V[:, j] if org is None else V[:, j].astype(np.float64) + org[j]
+        if normals is not None:
+            nv = normals.detach().cpu().numpy()
+            for j, a in enumerate(("nx", "ny", "nz")):
+                vt[a] = nv[:, j]
         if self.color_buffer is not None:
             c = np.ascontiguousarray(self.colors.cpu().numpy())
             with np.errstate(invalid="ignore"):

@@ -7,11 +7,15 @@ in the same run on the same box, ROUNDS times after a warm-up:
   components   Mesh.components()                              against  the numpy pass tests/mesh_np.components on the host's F
   clean        Mesh.clean(min_triangles=64, largest=1), the components handed in      (no host spelling exists; for scale only)
   save_ply     Mesh.save_ply (host clock, the copy included)  against  TriangleSoup.save_ply(weld=True)
+  decimate     Mesh.decimate at cell = 2 x and 4 x the voxel  against  the numpy restatement tests/mesh_simplify_np.decimate
+  vertex_faces Mesh.vertex_faces()                            against  mesh_simplify_np.vertex_faces (a stable argsort)
+  normals      Mesh.vertex_normals(), with and without a prebuilt adjacency      against  mesh_simplify_np.vertex_normals
 
 and checks that both sides describe the same mesh: byte-sorted device V equals the host weld's V, the numpy labels equal the
-device's. Per entry point it reports the time, the ALGORITHMIC bytes (every input read once, every output written once) over
+device's, and the restatement's bytes equal the device's for the three new stages. Per entry point it reports the time, the ALGORITHMIC bytes (every input read once, every output written once) over
 8 TB/s, and for the weld the table's load factor (unique vertices / slots) and the mean probe length (a second, untimed weld with
-probe_stats=True). Per kernel times come from torch.profiler when it can see the library's launches.
+probe_stats=True); for the decimation the same of its cluster table, and per kernel the algorithmic bytes over the
+kernel's own time. Per kernel times come from torch.profiler when it can see the library's launches.
 Exits with status 1 unless every comparison holds.
 
 usage: python tools/bench_mesh.py [--out FILE] [--only city|wavy]      env: ROUNDS=3 VIEWS=24 SIZE=1024 CELLS=1024 DIMS=512,512,128"""
@@ -31,13 +35,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bench_geometry as bg  # noqa: E402
 import geometry_np as gnp  # noqa: E402
 import mesh_np as mnp  # noqa: E402
+import mesh_simplify_np as snp  # noqa: E402
 import tsdf_np as tnp  # noqa: E402
 from sfgs.tsdf import TsdfVolume  # noqa: E402
 
 ROUNDS = bg.ROUNDS
 DIMS = tuple(int(v) for v in os.environ.get("DIMS", "512,512,128").split(","))
 HBM_BYTES_PER_S = 8.0e12
-KERNELS = ("weld_", "cc_", "clean_", "compact_", "mesh_")
+KERNELS = ("weld_", "cc_", "clean_", "compact_", "mesh_", "dec_", "vf_", "vn_")
 
 
 def device_ms(fn):
@@ -68,7 +73,7 @@ def city_soup():
     voxel = bg.CELLS * bg.RES / nx
     vol = TsdfVolume((0.0, 0.0, float(np.floor(terrain.min())) - 8.0 * voxel), DIMS, voxel, 3.0 * voxel, max_weight=64.0, device="cuda")
     vol.add_views(depths, cams)
-    return vol.extract(16 * nx * ny)
+    return vol.extract(16 * nx * ny), voxel, tuple(float(v) for v in vol.origin)
 
 
 def wavy_soup():
@@ -76,7 +81,7 @@ def wavy_soup():
     nz, ny, nx = tsdf.shape
     vol = TsdfVolume(origin, (nx, ny, nz), voxel, trunc=1.0, colors=True, device="cuda")
     vol.load(torch.from_numpy(tsdf).cuda(), torch.from_numpy(weight).cuda(), torch.from_numpy(rgb).cuda())
-    return vol.extract(200_000)
+    return vol.extract(200_000), float(voxel), tuple(float(v) for v in origin)
 
 
 def kernel_times(fn):
@@ -107,7 +112,99 @@ def stage(name, algorithmic_bytes, device_times, host_times, timed_as):
     return name, r
 
 
-def run(soup, tmp):
+def per_kernel(times, bytes_of):
+    """kernel name -> {us, algorithmic_bytes, share_of_8_TB_per_s} for the kernels whose bytes are stated"""
+    if not isinstance(times, dict):
+        return times
+    out = {}
+    for name, us in times.items():
+        key = next((k for k in bytes_of if name.endswith(k) or k in name), None)
+        out[name] = {"us": us}
+        if key is not None and us > 0:
+            out[name].update({"algorithmic_bytes": bytes_of[key], "share_of_8_TB_per_s": bytes_of[key] / (us * 1e-6) / HBM_BYTES_PER_S})
+    return out
+
+
+def same_bytes(t, a):
+    return bool(t.cpu().numpy().tobytes() == np.ascontiguousarray(a).tobytes())
+
+
+def run_simplify(mesh, voxel, origin):
+    """The decimation, adjacency and normal stages on a welded mesh -> (stages, details, every comparison held)"""
+    m, n = int(mesh.num_vertices), int(mesh.num_faces)
+    k = 2 if mesh.color_buffer is not None else 1
+    V, F = mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy()
+    C = None if mesh.color_buffer is None else mesh.colors.cpu().numpy()
+    stages, details, equal = {}, {}, True
+    for factor in (2, 4):
+        cell = factor * voxel
+        mesh.decimate(cell, origin)                                                    # warm-up
+        t_dev, t_host = [], []
+        for r in range(ROUNDS):
+            print(f"bench_mesh: decimate at {factor} voxels, round {r + 1} of {ROUNDS}", file=sys.stderr, flush=True)
+            (out, vmap), ms = device_ms(lambda: mesh.decimate(cell, origin, return_map=True))
+            t_dev.append(ms)
+            want, ms = host_ms(lambda: snp.decimate(V, F, C, cell, origin))
+            t_host.append(ms)
+            equal &= same_bytes(out.vertices, want[0]) and same_bytes(out.faces, want[1]) and same_bytes(vmap, want[3])
+            equal &= C is None or same_bytes(out.colors, want[2])
+        info = want[4]
+        kv, kf, K = len(want[0]), len(want[1]), info["clusters"]
+        probed = mesh.decimate(cell, origin, probe_stats=True)
+        slots = 64
+        while slots < 6 * ((m + 2) // 3):
+            slots *= 2
+        name = f"decimate_{factor}_voxels"
+        stages.update([stage(name, 12 * m * k + 12 * n + 12 * kv * k + 12 * kf, t_dev, t_host,
+                             f"device: events around Mesh.decimate(cell={factor} voxels, return_map=True); host: mesh_simplify_np.decimate")])
+        kernel_bytes = {"dec_cell_kernel": 12 * m + 13 * m, "weld_insert_kernel": 13 * m + 8 * m, "dec_rep_kernel": 10 * m,
+                        "dec_sum_kernel": 12 * m * k + 8 * m + 4 * m + 28 * m + 24 * m * (k - 1), "dec_face_kernel": 24 * n + 26 * n,
+                        "dec_mark_kernel": 13 * n, "dec_resolve_kernel": m + K * (12 + 24 * k + 12 * k), "clean_faces_kernel": n + 40 * kf,
+                        "dec_map_kernel": 13 * m}
+        details[name] = {"cell": cell, "clusters": K, "single_member_clusters": info["single"], "collapsed_faces": info["collapsed"],
+                         "duplicate_faces": info["duplicates"], "unreferenced_clusters": info["unreferenced"],
+                         "output": {"vertices": kv, "faces": kf, "faces_kept_share": kf / max(n, 1)},
+                         "cluster_table": {"slots": slots, "load_factor": K / slots, "mean_probe_length": probed.weld_probes / max(m, 1)},
+                         "kernels": per_kernel(kernel_times(lambda: mesh.decimate(cell, origin)), kernel_bytes),
+                         "note": "weld_insert_kernel / dec_rep_kernel run twice (cells, then sorted triples): their times are the "
+                                 "sums, their bytes those of the vertex pass"}
+    adj = mesh.vertex_faces()
+    mesh.vertex_normals(adj)
+    mesh.vertex_normals()
+    t_vf, t_vf_host, t_vn, t_vn_adj, t_vn_host = [], [], [], [], []
+    for r in range(ROUNDS):
+        print(f"bench_mesh: adjacency and normals, round {r + 1} of {ROUNDS}", file=sys.stderr, flush=True)
+        got, ms = device_ms(lambda: mesh.vertex_faces())
+        t_vf.append(ms)
+        want, ms = host_ms(lambda: snp.vertex_faces(F, m))
+        t_vf_host.append(ms)
+        equal &= same_bytes(got.offsets, want[0]) and same_bytes(got.records, want[1]) and got.check() == 0
+        normals, ms = device_ms(lambda: mesh.vertex_normals())
+        t_vn.append(ms)
+        with_adj, ms = device_ms(lambda: mesh.vertex_normals(adj))
+        t_vn_adj.append(ms)
+        want_n, ms = host_ms(lambda: snp.vertex_normals(V, F, want))
+        t_vn_host.append(ms)
+        equal &= same_bytes(normals, want_n) and same_bytes(with_adj, want_n)
+    stages.update([
+        stage("vertex_faces", 12 * n + 4 * m + 12 * n, t_vf, t_vf_host, "device: events around Mesh.vertex_faces(); host: stable argsort + bincount"),
+        stage("vertex_normals", 12 * n + 12 * m + 12 * m, t_vn, t_vn_host,
+              "device: events around Mesh.vertex_normals(), the adjacency built in the call; host: mesh_simplify_np.vertex_normals, adjacency given"),
+        stage("vertex_normals_prebuilt_adjacency", 4 * m + 12 * n + 12 * n + 12 * m + 12 * m, t_vn_adj, t_vn_host,
+              "device: events around Mesh.vertex_normals(adjacency); host: as above"),
+    ])
+    valence = np.diff(want[0])
+    details["adjacency"] = {"max_valence": int(valence.max()), "mean_valence": float(valence.mean()),
+                            "kernels": per_kernel(kernel_times(lambda: mesh.vertex_faces()),
+                                                  {"vf_count_kernel": 12 * n + 4 * m, "vf_fill_kernel": 12 * n + 4 * m + 12 * n,
+                                                   "vf_sort_kernel": 4 * m + 24 * n, "vf_offsets_kernel": 12 * m})}
+    # the normal kernel reads per record a face (12 bytes) and three positions (36 bytes): gathers; algorithmic = each once
+    details["normals"] = {"kernels": per_kernel(kernel_times(lambda: mesh.vertex_normals(adj)), {"vn_kernel": 4 * m + 24 * n + 24 * m}),
+                          "gathered_bytes": 4 * m + 3 * n * (4 + 12 + 36) + 12 * m}
+    return stages, details, equal
+
+
+def run(soup, tmp, voxel=None, origin=None):
     from sfgs.mesh import weld
     n = int(soup.num_triangles)
     assert n <= soup.capacity, (n, soup.capacity)
@@ -157,7 +254,10 @@ def run(soup, tmp):
         stage("save_ply", 12 * m * k + 12 * n, t_ply, t_ply_host,
               "host clock; device: Mesh.save_ply, the copy of V, F and colours included; host: TriangleSoup.save_ply(weld=True)"),
     ])
+    simplify_stages, simplify, equal_simplify = run_simplify(mesh, voxel, origin)
+    stages.update(simplify_stages)
     return {"triangles": n, "soup_records": 3 * n, "welded_vertices": m, "components": count, "colours": colours,
+            "simplify": simplify, "equal_simplify": equal_simplify,
             "cleaned": {"vertices": kept_v, "faces": kept_f},
             "weld_table": {"slots": slots, "load_factor": m / slots, "mean_probe_length": probed.weld_probes / (3 * n)},
             "stages": stages, "equal_weld": equal_weld, "equal_labels": equal_labels,
@@ -172,14 +272,15 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         for name, make in (("wavy", wavy_soup), ("city", city_soup)):
             if only in (None, name):
-                result[name] = run(make(), tmp)
+                soup, voxel, origin = make()
+                result[name] = run(soup, tmp, voxel, origin)
     text = json.dumps(result, indent=1)
     print(text)
     if out_path:
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "w") as f:
             f.write(text + "\n")
-    ok = all(result[k]["equal_weld"] and result[k]["equal_labels"] for k in ("wavy", "city") if k in result)
+    ok = all(result[k]["equal_weld"] and result[k]["equal_labels"] and result[k]["equal_simplify"] for k in ("wavy", "city") if k in result)
     sys.exit(0 if ok else 1)
 
 
