@@ -5,11 +5,12 @@
 // learn the output size. Here: ONE prefix scan of the mask (one host read-back: the kept-row count, needed to size the
 // outputs) and ONE multi-tensor gather launch. Pure data movement: bit-exact by construction.
 #include "sfgs_internal.h"
+#include "row_table.h"
+#include "scan.h"
 
 namespace sfgs {
 
 constexpr int CP_MAX_TENSORS = 48;
-constexpr int CP_WORDS_PER_THREAD = 8, CP_WORD_CHUNK = CP_NT * CP_WORDS_PER_THREAD;
 
 // CompactScratch / cp_blocks / cp_scratch_bytes / cp_view: sfgs_internal.h (mesh.hip reads a plan's ranks too)
 
@@ -26,21 +27,6 @@ compact_count_kernel(const unsigned char* __restrict__ keep, long long N, unsign
   unsigned total;
   block_excl_scan_u32<CP_NT>(c, &total, smem);
   if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(1024)
-compact_scan_blocks_kernel(unsigned* __restrict__ block_sum, long long NB, unsigned long long* __restrict__ total_out) {
-  __shared__ unsigned smem[1024 / 64 + 1];
-  unsigned long long carry = 0;
-  for (long long b0 = 0; b0 < NB; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const unsigned v = i < NB ? block_sum[i] : 0u;
-    unsigned total;
-    const unsigned ex = block_excl_scan_u32<1024>(v, &total, smem);
-    if (i < NB) block_sum[i] = (unsigned)carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = carry;
 }
 
 __global__ void __launch_bounds__(CP_NT)
@@ -62,58 +48,33 @@ compact_index_kernel(const unsigned char* __restrict__ keep, long long N, const 
     if (base + k < N) { dst_index[base + k] = pos; pos += (flags >> k) & 1u; }
 }
 
-struct CompactTable {
-  const void* src[CP_MAX_TENSORS];
-  void* dst[CP_MAX_TENSORS];
-  unsigned row_units[CP_MAX_TENSORS];   // row size in units of U
-  unsigned block_end[CP_MAX_TENSORS];
-  int count;
-};
+using CompactTable = RowTable<CP_MAX_TENSORS>;
 
 template <typename U>
-__global__ void __launch_bounds__(CP_NT)
+__global__ void __launch_bounds__(RT_NT)
 compact_gather_kernel(const CompactTable tab, const unsigned char* __restrict__ keep,
                       const unsigned* __restrict__ dst_index, long long N) {
-  int ti = 0;
-  while (ti + 1 < tab.count && blockIdx.x >= tab.block_end[ti]) ++ti;
-  const unsigned first = ti ? tab.block_end[ti - 1] : 0u;
-  const unsigned ru = tab.row_units[ti];
-  const U* __restrict__ src = (const U*)tab.src[ti];
-  U* __restrict__ dst = (U*)tab.dst[ti];
-  const long long words = N * (long long)ru;
-  const long long base = (long long)(blockIdx.x - first) * CP_WORD_CHUNK;   // block-uniform
-  const long long row0 = base / ru;                                         // one 64-bit division per block
-  const unsigned rem0 = (unsigned)(base - row0 * ru);
-  const float inv = 1.0f / (float)ru;
   // three phases so that every load of the thread is in flight before the first use: rows and keep flags, then
   // destination rows and source words (unconditional, from clamped indices), then the predicated stores. (One loop with
   // `if (keep[row]) dst[..dst_index[row]..] = src[w]` serialises three dependent round trips per word.)
-  long long rowv[CP_WORDS_PER_THREAD];
-  unsigned colv[CP_WORDS_PER_THREAD];
-  unsigned char kp[CP_WORDS_PER_THREAD];
+  long long rowv[RT_WORDS_PER_THREAD];
+  unsigned colv[RT_WORDS_PER_THREAD];
+  unsigned char kp[RT_WORDS_PER_THREAD];
+  const RowWalk rw = row_table_walk(tab, N, keep, rowv, colv, kp);
+  const U* __restrict__ src = (const U*)rw.src;
+  U* __restrict__ dst = (U*)rw.dst;
+  U val[RT_WORDS_PER_THREAD];
+  unsigned di[RT_WORDS_PER_THREAD];
 #pragma unroll
-  for (int k = 0; k < CP_WORDS_PER_THREAD; ++k) {
-    const unsigned off = threadIdx.x + k * CP_NT;
-    // (rem0 + off) / ru with x < 2^24: float estimate + one correction step is exact
-    const unsigned x = rem0 + off;
-    unsigned q = (unsigned)((float)x * inv);
-    if (q * ru > x) --q; else if ((q + 1) * ru <= x) ++q;
-    rowv[k] = min(row0 + (long long)q, N - 1);
-    colv[k] = x - q * ru;
-    kp[k] = keep[rowv[k]];
-  }
-  U val[CP_WORDS_PER_THREAD];
-  unsigned di[CP_WORDS_PER_THREAD];
-#pragma unroll
-  for (int k = 0; k < CP_WORDS_PER_THREAD; ++k) {
-    const long long w = min(base + (long long)(threadIdx.x + k * CP_NT), words - 1);
+  for (int k = 0; k < RT_WORDS_PER_THREAD; ++k) {
+    const long long w = min(rw.base + (long long)(threadIdx.x + k * RT_NT), rw.words - 1);
     val[k] = src[w];
     di[k] = dst_index[rowv[k]];
   }
 #pragma unroll
-  for (int k = 0; k < CP_WORDS_PER_THREAD; ++k) {
-    const long long w = base + (long long)(threadIdx.x + k * CP_NT);
-    if (w < words && kp[k]) dst[(long long)di[k] * ru + colv[k]] = val[k];
+  for (int k = 0; k < RT_WORDS_PER_THREAD; ++k) {
+    const long long w = rw.base + (long long)(threadIdx.x + k * RT_NT);
+    if (w < rw.words && kp[k]) dst[(long long)di[k] * rw.ru + colv[k]] = val[k];
   }
 }
 
@@ -136,7 +97,8 @@ extern "C" int sfgs_compact_plan(const unsigned char* keep, int64_t N, void* scr
     const long long NB = cp_blocks(N);
     { ProfScope ps_(KID_COMPACT_SCAN, stream);
       hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)NB), dim3(CP_NT), 0, stream, keep, (long long)N, s.block_sum);
-      hipLaunchKernelGGL(compact_scan_blocks_kernel, dim3(1), dim3(1024), 0, stream, s.block_sum, NB, s.total);
+      hipLaunchKernelGGL(scan_sums_kernel<unsigned>, dim3(1), dim3(SCAN_TOP_THREADS), 0, stream, s.block_sum, NB, 1,
+                         (const unsigned long long*)nullptr, s.total);
       hipLaunchKernelGGL(compact_index_kernel, dim3((unsigned)NB), dim3(CP_NT), 0, stream, keep, (long long)N,
                          s.block_sum, s.dst_index); }
     SFGS_POST_LAUNCH("compact_scan", stream, 0);
@@ -168,23 +130,12 @@ extern "C" int sfgs_compact_rows(const unsigned char* keep, int64_t N, const voi
   int i = 0;
   while (i < count) {
     CompactTable tab;
-    tab.count = 0;
-    uint64_t blocks = 0;
-    for (; i < count && tab.count < CP_MAX_TENSORS; ++i) {
-      if (tensors[i].row_bytes == 0) continue;
-      const uint64_t ru = (uint64_t)tensors[i].row_bytes / unit;
-      const uint64_t nb = ((uint64_t)N * ru + CP_WORD_CHUNK - 1) / CP_WORD_CHUNK;
-      SFGS_REQUIRE(nb < (1ull << 31), SFGS_E_UNSUPPORTED, "tensor %d: too large for one launch", i);
-      if (blocks + nb >= (1ull << 31)) break;
-      blocks += nb;
-      tab.src[tab.count] = tensors[i].src; tab.dst[tab.count] = tensors[i].dst;
-      tab.row_units[tab.count] = (unsigned)ru; tab.block_end[tab.count] = (unsigned)blocks;
-      ++tab.count;
-    }
-    if (!blocks) continue;
+    uint64_t blocks;
+    if (const int rc = row_table_pack(tensors, count, i, N, unit, &tab, &blocks, &i)) return rc;
+    if (!blocks) break;
     { ProfScope ps_(KID_COMPACT_GATHER, stream);
-      if (words_ok) hipLaunchKernelGGL(compact_gather_kernel<uint32_t>, dim3((unsigned)blocks), dim3(CP_NT), 0, stream, tab, keep, s.dst_index, (long long)N);
-      else hipLaunchKernelGGL(compact_gather_kernel<unsigned char>, dim3((unsigned)blocks), dim3(CP_NT), 0, stream, tab, keep, s.dst_index, (long long)N); }
+      if (words_ok) hipLaunchKernelGGL(compact_gather_kernel<uint32_t>, dim3((unsigned)blocks), dim3(RT_NT), 0, stream, tab, keep, s.dst_index, (long long)N);
+      else hipLaunchKernelGGL(compact_gather_kernel<unsigned char>, dim3((unsigned)blocks), dim3(RT_NT), 0, stream, tab, keep, s.dst_index, (long long)N); }
     SFGS_POST_LAUNCH("compact_gather", stream, 0);
   }
   return SFGS_OK;

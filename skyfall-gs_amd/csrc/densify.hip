@@ -21,6 +21,8 @@
 // methods); the children's positions use the caller's normal samples (torch.randn on the device: the reference draws
 // from the same generator, so the random stream differs in order only).
 #include "sfgs_internal.h"
+#include "row_table.h"
+#include "scan.h"
 
 namespace sfgs {
 
@@ -176,23 +178,6 @@ densify_decide_kernel(long long N, const float* __restrict__ gnorm, const float*
   }
 }
 
-__global__ void __launch_bounds__(1024)
-densify_scan_blocks_kernel(unsigned* __restrict__ block_sum, long long NB, unsigned long long* __restrict__ totals) {
-  __shared__ unsigned smem[1024 / 64 + 1];
-  for (int k = 0; k < DN_CATS; ++k) {
-    unsigned long long carry = 0;
-    for (long long b0 = 0; b0 < NB; b0 += 1024) {
-      const long long i = b0 + threadIdx.x;
-      const unsigned v = i < NB ? block_sum[i * DN_CATS + k] : 0u;
-      unsigned total;
-      const unsigned ex = block_excl_scan_u32<1024>(v, &total, smem);
-      if (i < NB) block_sum[i * DN_CATS + k] = (unsigned)carry + ex;
-      carry += total;
-    }
-    if (threadIdx.x == 0) totals[k] = carry;
-  }
-}
-
 __global__ void __launch_bounds__(DN_NT)
 densify_index_kernel(long long N, const unsigned char* __restrict__ code, const unsigned* __restrict__ block_sum,
                      unsigned* __restrict__ idx /* [N][4]: orig, clone, child (kept ranks), split (raw rank) */) {
@@ -209,54 +194,35 @@ densify_index_kernel(long long N, const unsigned char* __restrict__ code, const 
 }
 
 constexpr int DG_MAX_TENSORS = 40;
-constexpr int DG_WORDS_PER_THREAD = 8, DG_WORD_CHUNK = DN_NT * DG_WORDS_PER_THREAD;
 struct DensifyTable {
-  const void* src[DG_MAX_TENSORS];
-  void* dst[DG_MAX_TENSORS];
-  unsigned row_units[DG_MAX_TENSORS];   // 4-byte words per row
+  RowTable<DG_MAX_TENSORS> rows;        // 4-byte words
   unsigned zero_new[DG_MAX_TENSORS];    // 1: new rows (clones, children) are zero (Adam moments)
-  unsigned block_end[DG_MAX_TENSORS];
-  int count;
 };
 
-__global__ void __launch_bounds__(DN_NT)
+__global__ void __launch_bounds__(RT_NT)
 densify_gather_kernel(const DensifyTable tab, long long N, const unsigned char* __restrict__ code,
                       const unsigned* __restrict__ idx, unsigned n_orig, unsigned n_clone, unsigned n_child) {
-  int ti = 0;
-  while (ti + 1 < tab.count && blockIdx.x >= tab.block_end[ti]) ++ti;
-  const unsigned first = ti ? tab.block_end[ti - 1] : 0u;
-  const unsigned ru = tab.row_units[ti];
-  const bool zero_new = tab.zero_new[ti] != 0;
-  const uint32_t* __restrict__ src = (const uint32_t*)tab.src[ti];
-  uint32_t* __restrict__ dst = (uint32_t*)tab.dst[ti];
-  const long long words = N * (long long)ru;
-  const long long base = (long long)(blockIdx.x - first) * DG_WORD_CHUNK;
-  const long long row0 = base / ru;
-  const unsigned rem0 = (unsigned)(base - row0 * ru);
-  const float inv = 1.0f / (float)ru;
   // loads first (row codes; then source words and target indices, unconditional from clamped indices), stores last: one
   // loop with the loads under `if (code & ...)` serialises three dependent round trips to memory per word
-  long long rowv[DG_WORDS_PER_THREAD];
-  unsigned colv[DG_WORDS_PER_THREAD], cv[DG_WORDS_PER_THREAD];
+  long long rowv[RT_WORDS_PER_THREAD];
+  unsigned colv[RT_WORDS_PER_THREAD];
+  unsigned char cv[RT_WORDS_PER_THREAD];
+  const RowWalk rw = row_table_walk(tab.rows, N, code, rowv, colv, cv);
+  const unsigned ru = rw.ru;
+  const long long base = rw.base, words = rw.words;
+  const bool zero_new = tab.zero_new[rw.ti] != 0;
+  const uint32_t* __restrict__ src = (const uint32_t*)rw.src;
+  uint32_t* __restrict__ dst = (uint32_t*)rw.dst;
+  uint32_t val[RT_WORDS_PER_THREAD];
+  uint4 ixv[RT_WORDS_PER_THREAD];
 #pragma unroll
-  for (int k = 0; k < DG_WORDS_PER_THREAD; ++k) {
-    const unsigned x = rem0 + threadIdx.x + k * DN_NT;
-    unsigned q = (unsigned)((float)x * inv);
-    if (q * ru > x) --q; else if ((q + 1) * ru <= x) ++q;
-    rowv[k] = min(row0 + (long long)q, N - 1);
-    colv[k] = x - q * ru;
-    cv[k] = code[rowv[k]];
-  }
-  uint32_t val[DG_WORDS_PER_THREAD];
-  uint4 ixv[DG_WORDS_PER_THREAD];
-#pragma unroll
-  for (int k = 0; k < DG_WORDS_PER_THREAD; ++k) {
-    val[k] = src[min(base + (long long)(threadIdx.x + k * DN_NT), words - 1)];
+  for (int k = 0; k < RT_WORDS_PER_THREAD; ++k) {
+    val[k] = src[min(base + (long long)(threadIdx.x + k * RT_NT), words - 1)];
     ixv[k] = *reinterpret_cast<const uint4*>(idx + 4 * rowv[k]);
   }
 #pragma unroll
-  for (int k = 0; k < DG_WORDS_PER_THREAD; ++k) {
-    const long long w = base + (long long)(threadIdx.x + k * DN_NT);
+  for (int k = 0; k < RT_WORDS_PER_THREAD; ++k) {
+    const long long w = base + (long long)(threadIdx.x + k * RT_NT);
     const unsigned c = cv[k], col = colv[k];
     if (w < words && (c & (DN_KEEP_ORIG | DN_KEEP_CLONE | DN_KEEP_CHILD))) {
       const uint32_t nv = zero_new ? 0u : val[k];
@@ -380,7 +346,8 @@ extern "C" int sfgs_densify_decide(int64_t N, const float* grad_norm, const floa
       hipLaunchKernelGGL(densify_decide_kernel<float>, dim3((unsigned)NB), dim3(DN_NT), 0, stream, (long long)N, grad_norm,
                          grad_abs, scaling, (const float*)opacity, Q_dev, Q_host, max_grad, min_opacity, dense_threshold,
                          big_threshold, use_big_threshold, s.code, s.block_sum);
-    hipLaunchKernelGGL(densify_scan_blocks_kernel, dim3(1), dim3(1024), 0, stream, s.block_sum, NB, s.totals);
+    hipLaunchKernelGGL(scan_sums_kernel<unsigned>, dim3(1), dim3(SCAN_TOP_THREADS), 0, stream, s.block_sum, NB, DN_CATS,
+                       (const unsigned long long*)nullptr, s.totals);
     hipLaunchKernelGGL(densify_index_kernel, dim3((unsigned)NB), dim3(DN_NT), 0, stream, (long long)N, s.code, s.block_sum,
                        s.idx); }
   SFGS_POST_LAUNCH("densify_decide", stream, 0);
@@ -413,28 +380,24 @@ extern "C" int sfgs_densify_gather(int64_t N, const void* scratch, const int64_t
   SFGS_REQUIRE(scratch && tensors, SFGS_E_ARG, "NULL argument");
   hipStream_t stream = (hipStream_t)stream_;
   const DensifyScratch s = dn_view(const_cast<void*>(scratch), N);
+  for (int i = 0; i < count; ++i) {   // every tensor is checked before the first launch, as in sfgs_compact_rows
+    const SfgsDensifyTensor& t = tensors[i];
+    SFGS_REQUIRE(t.row_bytes >= 0 && t.row_bytes < (1ll << 22) && (t.row_bytes & 3) == 0, SFGS_E_ARG,
+                 "tensor %d: row size must be a multiple of 4 bytes", i);
+    if (t.row_bytes == 0) continue;
+    SFGS_REQUIRE(t.src && t.dst && (((uintptr_t)t.src | (uintptr_t)t.dst) & 3) == 0, SFGS_E_ARG, "tensor %d: bad pointer", i);
+  }
   int i = 0;
   while (i < count) {
     DensifyTable tab;
-    tab.count = 0;
-    uint64_t blocks = 0;
-    for (; i < count && tab.count < DG_MAX_TENSORS; ++i) {
-      const SfgsDensifyTensor& t = tensors[i];
-      SFGS_REQUIRE(t.row_bytes >= 0 && t.row_bytes < (1ll << 22) && (t.row_bytes & 3) == 0, SFGS_E_ARG,
-                   "tensor %d: row size must be a multiple of 4 bytes", i);
-      if (t.row_bytes == 0) continue;
-      SFGS_REQUIRE(t.src && t.dst && (((uintptr_t)t.src | (uintptr_t)t.dst) & 3) == 0, SFGS_E_ARG, "tensor %d: bad pointer", i);
-      const uint64_t ru = (uint64_t)t.row_bytes / 4;
-      const uint64_t nb = ((uint64_t)N * ru + DG_WORD_CHUNK - 1) / DG_WORD_CHUNK;
-      if (blocks + nb >= (1ull << 31)) break;
-      blocks += nb;
-      tab.src[tab.count] = t.src; tab.dst[tab.count] = t.dst; tab.row_units[tab.count] = (unsigned)ru;
-      tab.zero_new[tab.count] = t.zero_new_rows ? 1u : 0u; tab.block_end[tab.count] = (unsigned)blocks;
-      ++tab.count;
-    }
-    if (!blocks) continue;
+    uint64_t blocks;
+    int next;
+    if (const int rc = row_table_pack(tensors, count, i, N, 4, &tab.rows, &blocks, &next)) return rc;
+    for (int e = 0; i < next; ++i)   // the table's entries are the non-empty tensors of [i, next)
+      if (tensors[i].row_bytes) tab.zero_new[e++] = tensors[i].zero_new_rows ? 1u : 0u;
+    if (!blocks) break;
     { ProfScope ps_(KID_DENSIFY, stream);
-      hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)blocks), dim3(DN_NT), 0, stream, tab, (long long)N, s.code,
+      hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)blocks), dim3(RT_NT), 0, stream, tab, (long long)N, s.code,
                          s.idx, (unsigned)totals[0], (unsigned)totals[1], (unsigned)totals[2]); }
     SFGS_POST_LAUNCH("densify_gather", stream, 0);
   }

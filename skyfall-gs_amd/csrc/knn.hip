@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "sfgs_internal.h"
+#include "scan.h"
 
 namespace sfgs {
 
@@ -158,7 +159,7 @@ knn_count_kernel(const float* __restrict__ xyz, int N, int bits, const KnnBounds
   atomicAdd(&count[k], 1u);
 }
 
-// exclusive scan of M = nblk * 4096 counters: (a) per-block sums, (b) scan of the sums, (c) local scan + offset
+// exclusive scan of M = nblk * 4096 counters: (a) per-block sums, (b) scan of the sums (scan.h), (c) local scan + offset
 constexpr int KNN_SCAN_TILE = 4096;
 __global__ void __launch_bounds__(256)
 knn_scan_sums_kernel(const unsigned* __restrict__ count, unsigned* __restrict__ block_sum) {
@@ -170,18 +171,6 @@ knn_scan_sums_kernel(const unsigned* __restrict__ count, unsigned* __restrict__ 
   unsigned total;
   block_excl_scan_u32<256>(s, &total, sm);
   if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(1024)
-knn_scan_top_kernel(unsigned* __restrict__ block_sum, int nblk) {   // nblk <= 4096
-  __shared__ unsigned sm[20];
-  unsigned v[4], s = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int j = threadIdx.x * 4 + k; v[k] = j < nblk ? block_sum[j] : 0u; s += v[k]; }
-  unsigned total;
-  unsigned run = block_excl_scan_u32<1024>(s, &total, sm);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int j = threadIdx.x * 4 + k; if (j < nblk) block_sum[j] = run; run += v[k]; }
 }
 
 __global__ void __launch_bounds__(256)
@@ -404,7 +393,8 @@ extern "C" int sfgs_knn_dist2(const float* xyz, int32_t N, float* out, void* scr
   hipLaunchKernelGGL(knn_bounds_kernel, dim3(1), dim3(1024), 0, stream, xyz, N, s.bits, s.bounds);
   hipLaunchKernelGGL(knn_count_kernel, dim3(pb), dim3(256), 0, stream, xyz, N, s.bits, s.bounds, s.keys, s.count);
   hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(nblk), dim3(256), 0, stream, s.count, s.block_sum);
-  hipLaunchKernelGGL(knn_scan_top_kernel, dim3(1), dim3(1024), 0, stream, s.block_sum, nblk);
+  hipLaunchKernelGGL(scan_sums_kernel<unsigned>, dim3(1), dim3(SCAN_TOP_THREADS), 0, stream, s.block_sum, (long long)nblk, 1,
+                     (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
   hipLaunchKernelGGL(knn_scan_apply_kernel, dim3(nblk), dim3(256), 0, stream, s.count, s.block_sum, s.start);
   hipLaunchKernelGGL(knn_scatter_kernel, dim3(pb), dim3(256), 0, stream, xyz, N, s.keys, s.start, s.count, s.sorted);
   hipLaunchKernelGGL(knn_boxes_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, s.sorted, N, nullptr, nullptr, s.blo,

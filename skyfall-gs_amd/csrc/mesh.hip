@@ -8,7 +8,7 @@
 //        linear probing from mesh_hash(key). Empty slot: compare-and-swap q in. Occupied by p: compare the soup's words at p and q
 //        (the soup is read-only, so whatever index a slot ever held witnesses the slot's key); equal -> fetch_min(slot, q), done;
 //        else the next slot. The thread remembers its slot. After the kernel a key's slot holds rep = the key's smallest q.
-//     2. weld_rep_kernel     rep_of[q] = table[slot_of[q]] (in place), flag[q] = (rep_of[q] == q).
+//     2. weld_rep_kernel     rep_of[q] = table[slot_of[q]] (in place), flag[q] = (rep_of[q] == q). (1 and 2: mesh_key_pass.)
 //     3. the row compaction of compact.hip on the flags: its plan ranks the representatives in order of first appearance
 //        (vid = the exclusive rank), its gather writes V[vid] = S[rep] and colour[vid] = C[rep].
 //     4. weld_faces_kernel   F[q] = rank[rep_of[q]]; the count goes into the state.
@@ -25,17 +25,17 @@
 //   DECIMATE (sfgs_mesh_decimate): vertex clustering as a second weld, held to tests/mesh_simplify_np.py byte for byte.
 //     1. dec_cell_kernel     a thread per vertex: the int32 cell floor((x - origin) / cell) per axis, in float64; a vertex whose
 //        cell is not finite or leaves int32 is marked bad (MESH_ST_BAD_VERTEX) and takes no further part.
-//     2. weld_insert_kernel over the cells as m twelve-byte keys (bad ones skipped), dec_rep_kernel, the compaction's plan:
+//     2. weld_insert_kernel over the cells as m twelve-byte keys (bad ones skipped), weld_rep_kernel, the compaction's plan:
 //        cluster ranks in order of first appearance, exactly as the weld numbers its vertices.
 //     3. dec_sum_kernel      count and 64-bit fixed-point sums (position inside the cell, colour; floor(f 2^32)) per cluster by
 //        integer atomics, summed first over runs of a wave's lanes that share a cluster. Integers: no order can change a bit.
 //     4. dec_face_kernel     G = cluster_of[F]; bad or collapsed faces are skipped, the others leave their sorted triple; with
-//        drop_duplicates weld_insert_kernel / dec_rep_kernel run again over the triples and a face stays when it is its key's
+//        drop_duplicates weld_insert_kernel / weld_rep_kernel run again over the triples and a face stays when it is its key's
 //        smallest t. dec_mark_kernel marks the clusters of kept faces.
 //     5. the compaction ranks kept clusters and kept faces; dec_resolve_kernel writes a kept cluster's row from its sums (or
 //        copies its one member's bytes), clean_faces_kernel moves the faces through the ranks, dec_map_kernel writes the map.
 //   VERTEX_FACES (sfgs_mesh_vertex_faces): vf_count_kernel (integer atomics per corner record), an exclusive scan in the three
-//     launches of the compaction's plan, vf_fill_kernel through atomic cursors, vf_sort_kernel: a thread per vertex sorts its own
+//     launches of the compaction's plan (the middle one is scan.h's loop), vf_fill_kernel through atomic cursors, vf_sort_kernel: a thread per vertex sorts its own
 //     segment in place -- insertion sort up to MESH_SORT_SHORT records, heapsort beyond, trip bound 2 k (log2 k + 2).
 //   VERTEX_NORMALS (sfgs_mesh_vertex_normals): vn_kernel, a thread per vertex walks its sorted segment and sums the faces'
 //     area-weighted normals in float64 in that order: no atomics, the same bits run after run.
@@ -47,6 +47,7 @@
 // No profiler ids of its own (the compaction keeps its two).
 #include "sfgs_internal.h"
 #include "mesh_math.h"
+#include "scan.h"
 
 namespace sfgs {
 
@@ -102,11 +103,14 @@ weld_insert_kernel(const uint32_t* __restrict__ soup, long long Q, uint32_t* tab
   }
 }
 
+// skip (nullable; the decimation's mask): a skipped key has no representative (MESH_EMPTY) and no flag
 __global__ void __launch_bounds__(MESH_THREADS)
-weld_rep_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ slot_rep, unsigned char* __restrict__ flag, long long Q) {
+weld_rep_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ slot_rep, const unsigned char* __restrict__ skip,
+                unsigned char* __restrict__ flag, long long Q) {
   const long long q = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (q >= Q) return;
-  uint32_t rep = table[slot_rep[q]];
+  if (skip && skip[q]) { slot_rep[q] = MESH_EMPTY; flag[q] = 0; return; }
+  uint32_t rep = table[slot_rep[q]];                     // the slot is < slots: weld_insert_kernel
   if ((long long)rep >= Q) rep = (uint32_t)q;            // only after a probe bound (flagged): stay in range
   slot_rep[q] = rep;
   flag[q] = rep == (uint32_t)q ? 1 : 0;
@@ -316,19 +320,6 @@ dec_cell_kernel(const float* __restrict__ vertices, long long m, double ox, doub
   if (!ok) mesh_raise(state, MESH_ST_BAD_VERTEX);
 }
 
-// weld_rep_kernel under a skip mask: a skipped key has no representative (MESH_EMPTY) and no flag
-__global__ void __launch_bounds__(MESH_THREADS)
-dec_rep_kernel(const uint32_t* __restrict__ table, uint32_t* __restrict__ slot_rep, const unsigned char* __restrict__ skip,
-               unsigned char* __restrict__ flag, long long Q) {
-  const long long q = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
-  if (q >= Q) return;
-  if (skip[q]) { slot_rep[q] = MESH_EMPTY; flag[q] = 0; return; }
-  uint32_t rep = table[slot_rep[q]];                     // the slot is < slots: weld_insert_kernel
-  if ((long long)rep >= Q) rep = (uint32_t)q;            // only after a probe bound (flagged): stay in range
-  slot_rep[q] = rep;
-  flag[q] = rep == (uint32_t)q ? 1 : 0;
-}
-
 // cluster_of[v] = the first-appearance rank of v's cluster (-1: a bad vertex); the cluster's count and fixed-point sums take v's
 // share through integer atomics (order does not matter: integers), and the cluster's representative leaves its own index.
 // WAVE_FIRST: neighbouring vertices of a welded soup often share a cell, so a wave first sums every RUN of consecutive lanes with
@@ -477,7 +468,7 @@ vf_count_kernel(const int32_t* __restrict__ faces, long long Q, long long m, uin
 }
 
 // the exclusive scan of the counts in the three launches of the row compaction's plan: sums per CP_CHUNK, ONE workgroup over the
-// sums 1024 at a time with a carry, then the offsets (and the fill's cursors, which start at them)
+// sums 1024 at a time with a carry (scan.h), then the offsets (and the fill's cursors, which start at them)
 __global__ void __launch_bounds__(CP_NT)
 vf_chunk_sum_kernel(const uint32_t* __restrict__ count, long long m, unsigned* __restrict__ block_sum) {
   __shared__ unsigned smem[CP_NT / 64 + 1];
@@ -490,19 +481,11 @@ vf_chunk_sum_kernel(const uint32_t* __restrict__ count, long long m, unsigned* _
   if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
 }
 
-__global__ void __launch_bounds__(1024)
+__global__ void __launch_bounds__(SCAN_TOP_THREADS)
 vf_scan_chunks_kernel(unsigned* __restrict__ block_sum, long long NB, int32_t* __restrict__ total_out) {
-  __shared__ unsigned smem[1024 / 64 + 1];
-  unsigned carry = 0;                                    // <= 3 n < 2^31
-  for (long long b0 = 0; b0 < NB; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const unsigned v = i < NB ? block_sum[i] : 0u;
-    unsigned total;
-    const unsigned ex = block_excl_scan_u32<1024>(v, &total, smem);
-    if (i < NB) block_sum[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = (int32_t)carry;     // offsets[m]
+  __shared__ unsigned smem[SCAN_TOP_THREADS / 64 + 1];
+  const unsigned long long total = scan_sums_excl(block_sum, NB, 1, 0ull, smem);     // <= 3 n < 2^31
+  if (threadIdx.x == 0) *total_out = (int32_t)total;     // offsets[m]
 }
 
 __global__ void __launch_bounds__(CP_NT)
@@ -655,6 +638,29 @@ int mesh_check_sizes(const char* what, int64_t m, int64_t n) {
   return SFGS_OK;
 }
 
+// One pass of the key table over Q twelve-byte keys (the weld's soup vertices, the decimation's cells, its sorted triples): the
+// table emptied, every key that `skip` (nullable) does not exclude inserted, then slot_rep[q] = the smallest q with q's key and
+// flag[q] = (that is q itself). rep_name: the rep launch's name in an error text.
+int mesh_key_pass(const uint32_t* keys, long long Q, uint32_t* table, unsigned long long slots, uint32_t* slot_rep,
+                  const unsigned char* skip, unsigned char* flag, long long* state, bool stats, const char* rep_name,
+                  hipStream_t stream) {
+  SFGS_CHECK_HIP(hipMemsetAsync(table, 0xff, (size_t)slots * 4, stream));
+  const dim3 grid(mesh_blocks(Q)), block(MESH_THREADS);
+  if (stats) hipLaunchKernelGGL(weld_insert_kernel<true>, grid, block, 0, stream, keys, Q, table, slots, slot_rep, state, skip);
+  else hipLaunchKernelGGL(weld_insert_kernel<false>, grid, block, 0, stream, keys, Q, table, slots, slot_rep, state, skip);
+  SFGS_POST_LAUNCH("weld_insert", stream, 0);
+  hipLaunchKernelGGL(weld_rep_kernel, grid, block, 0, stream, (const uint32_t*)table, slot_rep, skip, flag, Q);
+  SFGS_POST_LAUNCH(rep_name, stream, 0);
+  return SFGS_OK;
+}
+
+int mesh_sizes(long long* state, const unsigned long long* a, long long av, const unsigned long long* b, long long bv,
+               hipStream_t stream) {
+  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, a, av, b, bv);
+  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
+  return SFGS_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sfgs_mesh_weld_scratch_bytes(int64_t n) {
@@ -682,27 +688,17 @@ extern "C" int sfgs_mesh_weld(const float* soup, const float* soup_colors, int64
   const long long Q = 3 * (long long)n;
   const unsigned long long slots = mesh_weld_slots(n);
   SFGS_CHECK_HIP(hipMemsetAsync(state, 0, 32, stream));
-  SFGS_CHECK_HIP(hipMemsetAsync(w.table, 0xff, (size_t)slots * 4, stream));
   const dim3 grid(mesh_blocks(Q)), block(MESH_THREADS);
-  if (flags & 1)
-    hipLaunchKernelGGL(weld_insert_kernel<true>, grid, block, 0, stream, (const uint32_t*)soup, Q, w.table, slots, w.slot_rep, state,
-                       (const unsigned char*)nullptr);
-  else
-    hipLaunchKernelGGL(weld_insert_kernel<false>, grid, block, 0, stream, (const uint32_t*)soup, Q, w.table, slots, w.slot_rep, state,
-                       (const unsigned char*)nullptr);
-  SFGS_POST_LAUNCH("weld_insert", stream, 0);
-  hipLaunchKernelGGL(weld_rep_kernel, grid, block, 0, stream, (const uint32_t*)w.table, w.slot_rep, w.flag, Q);
-  SFGS_POST_LAUNCH("weld_rep", stream, 0);
+  if (const int rc = mesh_key_pass((const uint32_t*)soup, Q, w.table, slots, w.slot_rep, nullptr, w.flag, state, flags & 1, "weld_rep",
+                                   stream))
+    return rc;
   if (const int rc = sfgs_compact_plan(w.flag, Q, w.compact, w.compact_bytes, nullptr, stream_)) return rc;
   const SfgsCompactTensor rows[2] = {{soup, vertices, 12}, {soup_colors, colors, 12}};
   if (const int rc = sfgs_compact_rows(w.flag, Q, w.compact, rows, colors ? 2 : 1, stream_)) return rc;
   const CompactScratch plan = cp_view(w.compact, Q);
   hipLaunchKernelGGL(weld_faces_kernel, grid, block, 0, stream, (const uint32_t*)w.slot_rep, (const uint32_t*)plan.dst_index, faces, Q);
   SFGS_POST_LAUNCH("weld_faces", stream, 0);
-  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, (const unsigned long long*)plan.total, 0ll,
-                     (const unsigned long long*)nullptr, (long long)n);
-  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
-  return SFGS_OK;
+  return mesh_sizes(state, plan.total, 0, nullptr, n, stream);
 }
 
 extern "C" int sfgs_mesh_vet(const int32_t* faces, int64_t n, int64_t m, long long* state, void* stream_) {
@@ -710,9 +706,7 @@ extern "C" int sfgs_mesh_vet(const int32_t* faces, int64_t n, int64_t m, long lo
   SFGS_REQUIRE(state && (faces || n == 0), SFGS_E_ARG, "sfgs_mesh_vet: NULL argument");
   hipStream_t stream = (hipStream_t)stream_;
   SFGS_CHECK_HIP(hipMemsetAsync(state, 0, 32, stream));
-  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, (const unsigned long long*)nullptr, (long long)m,
-                     (const unsigned long long*)nullptr, (long long)n);
-  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
+  if (const int rc = mesh_sizes(state, nullptr, m, nullptr, n, stream)) return rc;
   if (n > 0) {
     hipLaunchKernelGGL(mesh_vet_kernel, dim3(mesh_blocks(n)), dim3(MESH_THREADS), 0, stream, faces, (long long)n, (long long)m, state);
     SFGS_POST_LAUNCH("mesh_vet", stream, 0);
@@ -801,10 +795,7 @@ extern "C" int sfgs_mesh_clean(const float* vertices, const float* colors, const
                        (const uint32_t*)pf.dst_index, (const uint32_t*)pv.dst_index, faces_out);
     SFGS_POST_LAUNCH("clean_faces", stream, 0);
   }
-  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, (const unsigned long long*)pv.total, 0ll,
-                     (const unsigned long long*)pf.total, 0ll);
-  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
-  return SFGS_OK;
+  return mesh_sizes(state, pv.total, 0, pf.total, 0, stream);
 }
 
 // ---- decimate, vertex_faces, vertex_normals ----------------------------------------------------------------------------------------
@@ -907,22 +898,13 @@ extern "C" int sfgs_mesh_decimate(const float* vertices, const float* colors, co
   const bool drop_duplicates = flags & 1, stats = flags & 2;
   const dim3 block(MESH_THREADS), vgrid(mesh_blocks(m)), fgrid(mesh_blocks(n));
   const unsigned long long vslots = mesh_key_slots(m), fslots = mesh_key_slots(n);
-  SFGS_CHECK_HIP(hipMemsetAsync(d.table, 0xff, (size_t)vslots * 4, stream));
   SFGS_CHECK_HIP(hipMemsetAsync(d.zero_from, 0, d.zero_bytes, stream));
   // clusters: cells, the weld's table over them, first-appearance ranks, sums
   hipLaunchKernelGGL(dec_cell_kernel, vgrid, block, 0, stream, vertices, (long long)m, origin_x, origin_y, origin_z, cell, d.cells,
                      d.bad, state);
   SFGS_POST_LAUNCH("dec_cell", stream, 0);
-  if (stats)
-    hipLaunchKernelGGL(weld_insert_kernel<true>, vgrid, block, 0, stream, (const uint32_t*)d.cells, (long long)m, d.table, vslots,
-                       d.rep_of, state, (const unsigned char*)d.bad);
-  else
-    hipLaunchKernelGGL(weld_insert_kernel<false>, vgrid, block, 0, stream, (const uint32_t*)d.cells, (long long)m, d.table, vslots,
-                       d.rep_of, state, (const unsigned char*)d.bad);
-  SFGS_POST_LAUNCH("weld_insert", stream, 0);
-  hipLaunchKernelGGL(dec_rep_kernel, vgrid, block, 0, stream, (const uint32_t*)d.table, d.rep_of, (const unsigned char*)d.bad, d.flag,
-                     (long long)m);
-  SFGS_POST_LAUNCH("dec_rep", stream, 0);
+  if (const int rc = mesh_key_pass((const uint32_t*)d.cells, m, d.table, vslots, d.rep_of, d.bad, d.flag, state, stats, "dec_rep", stream))
+    return rc;
   if (const int rc = sfgs_compact_plan(d.flag, m, d.plan_cluster, d.plan_m_bytes, nullptr, stream_)) return rc;
   const CompactScratch pc = cp_view(d.plan_cluster, m);
   hipLaunchKernelGGL(dec_sum_kernel<MESH_SUM_WAVE_FIRST>, vgrid, block, 0, stream, vertices, colors, (long long)m, origin_x, origin_y, origin_z, cell,
@@ -933,15 +915,9 @@ extern "C" int sfgs_mesh_decimate(const float* vertices, const float* colors, co
     hipLaunchKernelGGL(dec_face_kernel, fgrid, block, 0, stream, faces, (long long)n, (long long)m, (const int32_t*)d.cluster_of,
                        d.gfaces, d.keys, d.skip_face, d.keep_face, state);
     SFGS_POST_LAUNCH("dec_face", stream, 0);
-    if (drop_duplicates) {
-      SFGS_CHECK_HIP(hipMemsetAsync(d.table, 0xff, (size_t)fslots * 4, stream));
-      hipLaunchKernelGGL(weld_insert_kernel<false>, fgrid, block, 0, stream, (const uint32_t*)d.keys, (long long)n, d.table, fslots,
-                         d.face_rep, state, (const unsigned char*)d.skip_face);
-      SFGS_POST_LAUNCH("weld_insert", stream, 0);
-      hipLaunchKernelGGL(dec_rep_kernel, fgrid, block, 0, stream, (const uint32_t*)d.table, d.face_rep,
-                         (const unsigned char*)d.skip_face, d.keep_face, (long long)n);
-      SFGS_POST_LAUNCH("dec_rep", stream, 0);
-    }
+    if (drop_duplicates)
+      if (const int rc = mesh_key_pass(d.keys, n, d.table, fslots, d.face_rep, d.skip_face, d.keep_face, state, false, "dec_rep", stream))
+        return rc;
     hipLaunchKernelGGL(dec_mark_kernel, fgrid, block, 0, stream, (const int32_t*)d.gfaces, (const unsigned char*)d.keep_face,
                        (long long)n, (long long)m, d.keep_cluster);
     SFGS_POST_LAUNCH("dec_mark", stream, 0);
@@ -964,10 +940,7 @@ extern "C" int sfgs_mesh_decimate(const float* vertices, const float* colors, co
                        (const uint32_t*)pv.dst_index, (long long)m, vertex_map);
     SFGS_POST_LAUNCH("dec_map", stream, 0);
   }
-  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, (const unsigned long long*)pv.total, 0ll,
-                     (const unsigned long long*)pf.total, 0ll);
-  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
-  return SFGS_OK;
+  return mesh_sizes(state, pv.total, 0, pf.total, 0, stream);
 }
 
 extern "C" size_t sfgs_mesh_vertex_faces_scratch_bytes(int64_t m) {
@@ -988,9 +961,7 @@ extern "C" int sfgs_mesh_vertex_faces(const int32_t* faces, int64_t n, int64_t m
   SFGS_REQUIRE(scratch_bytes >= a.total, SFGS_E_ARG, "mesh vertex_faces scratch too small: %zu < %zu", scratch_bytes, a.total);
   hipStream_t stream = (hipStream_t)stream_;
   SFGS_CHECK_HIP(hipMemsetAsync(state, 0, 32, stream));
-  hipLaunchKernelGGL(mesh_sizes_kernel, dim3(1), dim3(1), 0, stream, state, (const unsigned long long*)nullptr, (long long)m,
-                     (const unsigned long long*)nullptr, (long long)n);
-  SFGS_POST_LAUNCH("mesh_sizes", stream, 0);
+  if (const int rc = mesh_sizes(state, nullptr, m, nullptr, n, stream)) return rc;
   if (n == 0) {                                          // every segment is empty
     SFGS_CHECK_HIP(hipMemsetAsync(offsets, 0, ((size_t)m + 1) * 4, stream));
     return SFGS_OK;
@@ -1001,7 +972,7 @@ extern "C" int sfgs_mesh_vertex_faces(const int32_t* faces, int64_t n, int64_t m
   hipLaunchKernelGGL(vf_count_kernel, rgrid, block, 0, stream, faces, Q, (long long)m, a.cursor, state);
   SFGS_POST_LAUNCH("vf_count", stream, 0);
   hipLaunchKernelGGL(vf_chunk_sum_kernel, dim3((unsigned)NB), dim3(CP_NT), 0, stream, (const uint32_t*)a.cursor, (long long)m, a.block_sum);
-  hipLaunchKernelGGL(vf_scan_chunks_kernel, dim3(1), dim3(1024), 0, stream, a.block_sum, NB, offsets + m);
+  hipLaunchKernelGGL(vf_scan_chunks_kernel, dim3(1), dim3(SCAN_TOP_THREADS), 0, stream, a.block_sum, NB, offsets + m);
   hipLaunchKernelGGL(vf_offsets_kernel, dim3((unsigned)NB), dim3(CP_NT), 0, stream, a.cursor, (long long)m, (const unsigned*)a.block_sum,
                      offsets);
   SFGS_POST_LAUNCH("vf_scan", stream, 0);

@@ -2,8 +2,8 @@
 // (evaluate_gs_geometry.py:132-215) and its np.vstack over the views (:776), without a host read per view.
 //   append, three launches per view (no kernel waits for another workgroup: a launch is cheaper than a hang):
 //     1. pc_count_kernel    a workgroup owns PC_THREADS consecutive pixels and writes how many of them are used;
-//     2. pc_scan_kernel     ONE workgroup scans the counts exclusively, PC_SCAN_THREADS at a time with a carry that starts at
-//                           the cloud's running total (the state word), leaves every workgroup's first ROW and advances the total;
+//     2. scan_sums_kernel   (scan.h) ONE workgroup scans the counts exclusively, PC_SCAN_THREADS at a time with a carry that starts
+//                           at the cloud's running total (the state word), leaves every workgroup's first ROW and advances the total;
 //     3. pc_scatter_kernel  recomputes validity, ranks the used pixels inside the workgroup (ballot + one LDS word per wave),
 //                           unprojects them (geo_unproject.h: geometry.hip's float64 sequence) into LDS and copies the
 //                           workgroup's run of rows out with consecutive lanes on consecutive words. Colours alike.
@@ -15,6 +15,7 @@
 // The kernels have no profiler ids (the id list of sfgs_profile_kernel_name is closed by the loss kernels).
 #include "sfgs_internal.h"
 #include "geo_unproject.h"
+#include "scan.h"
 
 #include <math.h>
 
@@ -22,7 +23,8 @@ namespace sfgs {
 
 constexpr int PC_THREADS = 256;            // pixels per workgroup of the count and scatter kernels
 constexpr int PC_WAVES = PC_THREADS / 64;
-constexpr int PC_SCAN_THREADS = 1024;      // counts the scan kernel takes per round of its loop
+constexpr int PC_SCAN_THREADS = 1024;      // counts the scan kernel takes per round of its loop (tests size a view by it)
+static_assert(PC_SCAN_THREADS == SCAN_TOP_THREADS, "the scan's round is scan.h's");
 constexpr int PC_BOUNDS_MAX_BLOCKS = 1024;
 
 struct PcView {
@@ -46,22 +48,6 @@ pc_count_kernel(const float* __restrict__ depth, const unsigned char* __restrict
     for (int w = 0; w < PC_WAVES; ++w) n += wave_n[w];
     blk[blockIdx.x] = n;
   }
-}
-
-// blk[b]: count -> first row of workgroup b; *state: rows seen before this view -> after it
-__global__ void __launch_bounds__(PC_SCAN_THREADS)
-pc_scan_kernel(unsigned long long* __restrict__ blk, long long nblk, unsigned long long* __restrict__ state) {
-  __shared__ unsigned smem[PC_SCAN_THREADS / 64 + 1];
-  unsigned long long carry = *state;       // read by every thread before the first barrier; written after the last
-  for (long long base = 0; base < nblk; base += PC_SCAN_THREADS) {
-    const long long i = base + threadIdx.x;
-    const unsigned c = i < nblk ? (unsigned)blk[i] : 0u;
-    unsigned total;                        // <= PC_SCAN_THREADS * PC_THREADS = 2^18
-    const unsigned before = block_excl_scan_u32<PC_SCAN_THREADS>(c, &total, smem);
-    if (i < nblk) blk[i] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *state = carry;
 }
 
 template <bool COLORS>
@@ -211,7 +197,9 @@ extern "C" int sfgs_pointcloud_append(const SfgsPointCloudViewArgs* a, double* p
   const dim3 grid((unsigned)nblk), block(PC_THREADS);
   hipLaunchKernelGGL(pc_count_kernel, grid, block, 0, stream, a->depth, a->mask, P, blk);
   SFGS_POST_LAUNCH("pc_count", stream, 0);
-  hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(PC_SCAN_THREADS), 0, stream, blk, nblk, state);
+  // blk[b]: count -> first row of workgroup b; *state: rows seen before this view -> after it (carry in and total out: one word)
+  hipLaunchKernelGGL(scan_sums_kernel<unsigned long long>, dim3(1), dim3(PC_SCAN_THREADS), 0, stream, blk, nblk, 1,
+                     (const unsigned long long*)state, state);
   SFGS_POST_LAUNCH("pc_scan", stream, 0);
   if (colors)
     hipLaunchKernelGGL(pc_scatter_kernel<true>, grid, block, 0, stream, a->depth, a->mask, a->image, v,

@@ -13,7 +13,7 @@
 //     1024 x 1024 into 512 x 512 x 128 voxels (tools/variants/tsdf_run_x.patch, profiles/r22_tsdf_ab.txt).
 //   extraction, three launches modelled on pc_count / pc_scan / pc_scatter (no kernel waits for another workgroup):
 //     1. tsdf_count_kernel  a workgroup owns TSDF_THREADS consecutive cells and writes how many triangles they hold (0 ... 12 each);
-//     2. tsdf_scan_kernel   ONE workgroup scans the counts exclusively, 1024 at a time with a carry, and leaves the total in *state;
+//     2. scan_sums_kernel   (scan.h) ONE workgroup scans the counts exclusively, 1024 at a time with a carry, and leaves the total in *state;
 //     3. tsdf_emit_kernel   recomputes the cells, ranks their triangles inside the workgroup and writes the workgroup's run.
 //     The soup is ordered by cell, tetrahedron, triangle. A row at or beyond `capacity` is not written; the state counts it.
 //   ray-casting, ONE launch per view (tsdf_math.h: tsdf_ray_pixel; tests/tsdf_raycast_np.py in numpy, held to it byte for byte):
@@ -31,6 +31,7 @@
 // a pixel against H x W before any load or store.
 // No profiler ids.
 #include "sfgs_internal.h"
+#include "scan.h"
 #include "tsdf_math.h"
 
 #include <math.h>
@@ -40,7 +41,6 @@ namespace sfgs {
 constexpr int TSDF_THREADS = 256;
 constexpr int TSDF_WAVES = TSDF_THREADS / 64;
 constexpr int TSDF_BRICK_X = 8, TSDF_BRICK_Y = 8, TSDF_BRICK_Z = 4;     // TSDF_THREADS voxels; a wave is one z-slab of it
-constexpr int TSDF_SCAN_THREADS = 1024;
 static_assert(TSDF_BRICK_X * TSDF_BRICK_Y == 64 && TSDF_BRICK_X * TSDF_BRICK_Y * TSDF_BRICK_Z == TSDF_THREADS, "a wave is a slab");
 
 // the table's record as the kernel reads it: the layout of SfgsTsdfView (checked below)
@@ -163,22 +163,6 @@ tsdf_count_kernel(TsdfCells g, const float* __restrict__ tsdf, const float* __re
     for (int w = 0; w < TSDF_WAVES; ++w) total += wave_n[w];
     blk[blockIdx.x] = total;
   }
-}
-
-// blk[b]: count -> first row of workgroup b; *state = the total (what was there before is not read)
-__global__ void __launch_bounds__(TSDF_SCAN_THREADS)
-tsdf_scan_kernel(unsigned long long* __restrict__ blk, long long nblk, unsigned long long* __restrict__ state) {
-  __shared__ unsigned smem[TSDF_SCAN_THREADS / 64 + 1];
-  unsigned long long carry = 0;
-  for (long long base = 0; base < nblk; base += TSDF_SCAN_THREADS) {
-    const long long i = base + threadIdx.x;
-    const unsigned c = i < nblk ? (unsigned)blk[i] : 0u;
-    unsigned total;                        // <= TSDF_SCAN_THREADS * TSDF_THREADS * 12 < 2^22
-    const unsigned before = block_excl_scan_u32<TSDF_SCAN_THREADS>(c, &total, smem);
-    if (i < nblk) blk[i] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *state = carry;
 }
 
 template <bool COLORS>
@@ -357,7 +341,9 @@ extern "C" int sfgs_tsdf_extract(const SfgsTsdfVolume* vol, float* vertices, flo
     hipLaunchKernelGGL(tsdf_count_kernel, grid, block, 0, stream, g, (const float*)vol->tsdf, (const float*)vol->weight, blk);
     SFGS_POST_LAUNCH("tsdf_count", stream, 0);
   }
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_SCAN_THREADS), 0, stream, blk, nblk, state);
+  // blk[b]: count -> first row of workgroup b; *state = the total (what was there before is not read)
+  hipLaunchKernelGGL(scan_sums_kernel<unsigned long long>, dim3(1), dim3(SCAN_TOP_THREADS), 0, stream, blk, nblk, 1,
+                     (const unsigned long long*)nullptr, state);
   SFGS_POST_LAUNCH("tsdf_scan", stream, 0);
   if (nblk > 0) {
     if (colors)

@@ -256,7 +256,7 @@ def _same_bits(o, want):
 
 @pytest.mark.parametrize("mask", ["random", "low", "high"])
 def test_compact_block_scan_second_round(mask):
-    """N = 4 194 304 + 4 097 = 4 198 401 rows = 1 026 blocks of CP_CHUNK = 4 096 rows: compact_scan_blocks_kernel scans 1 024
+    """N = 4 194 304 + 4 097 = 4 198 401 rows = 1 026 blocks of CP_CHUNK = 4 096 rows: scan_sums_kernel (csrc/scan.h) scans 1 024
     block sums per round, so blocks 1 024 and 1 025 are placed by the second round from the carry of the first. With
     everything kept below row 4 194 304 the carry is all there is; with everything kept above it, it must be zero."""
     from sfgs.compact import compact_rows

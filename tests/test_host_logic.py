@@ -270,12 +270,17 @@ def _csrc_sources():
 
 def test_makefile_lists_every_source():
     """A source file csrc/Makefile does not know would link without its kernels' flags, or not at all: every *.hip / *.cpp of
-    csrc/ is in SRCS, and every file FLAG_FILES or a per-file `CXXFLAGS +=` rule names is one of SRCS."""
+    csrc/ is in SRCS, and every file FLAG_FILES or a per-file `CXXFLAGS +=` rule names is one of SRCS. A header it does not know
+    leaves stale objects behind after an edit: every *.h of csrc/ is in HDRS, and every file HDRS names exists."""
     mk = open(os.path.join(CSRC, "Makefile")).read()
     var = lambda name: re.search(r"^%s\s*=(.*)$" % name, mk, re.M).group(1).split()
     srcs = var("SRCS")
     assert len(srcs) == len(set(srcs))
     assert sorted(srcs) == _csrc_sources()
+    hdrs = var("HDRS")
+    assert len(hdrs) == len(set(hdrs))
+    assert sorted(h for h in hdrs if "/" not in h) == sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
+    assert all(os.path.isfile(os.path.join(CSRC, h)) for h in hdrs), hdrs
     assert var("FLAG_FILES") and set(var("FLAG_FILES")) <= set(srcs)
     rules = re.findall(r"^((?:_obj/\S+\.o\s*)+):\s*CXXFLAGS\s*\+=", mk, re.M)
     named = [t[len("_obj/"):-len(".o")] for r in rules for t in r.split()]

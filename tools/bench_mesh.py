@@ -42,7 +42,7 @@ from sfgs.tsdf import TsdfVolume  # noqa: E402
 ROUNDS = bg.ROUNDS
 DIMS = tuple(int(v) for v in os.environ.get("DIMS", "512,512,128").split(","))
 HBM_BYTES_PER_S = 8.0e12
-KERNELS = ("weld_", "cc_", "clean_", "compact_", "mesh_", "dec_", "vf_", "vn_")
+KERNELS = ("weld_", "cc_", "clean_", "compact_", "scan_sums_", "mesh_", "dec_", "vf_", "vn_")
 
 
 def device_ms(fn):
@@ -157,7 +157,7 @@ def run_simplify(mesh, voxel, origin):
         name = f"decimate_{factor}_voxels"
         stages.update([stage(name, 12 * m * k + 12 * n + 12 * kv * k + 12 * kf, t_dev, t_host,
                              f"device: events around Mesh.decimate(cell={factor} voxels, return_map=True); host: mesh_simplify_np.decimate")])
-        kernel_bytes = {"dec_cell_kernel": 12 * m + 13 * m, "weld_insert_kernel": 13 * m + 8 * m, "dec_rep_kernel": 10 * m,
+        kernel_bytes = {"dec_cell_kernel": 12 * m + 13 * m, "weld_insert_kernel": 13 * m + 8 * m, "weld_rep_kernel": 10 * m,
                         "dec_sum_kernel": 12 * m * k + 8 * m + 4 * m + 28 * m + 24 * m * (k - 1), "dec_face_kernel": 24 * n + 26 * n,
                         "dec_mark_kernel": 13 * n, "dec_resolve_kernel": m + K * (12 + 24 * k + 12 * k), "clean_faces_kernel": n + 40 * kf,
                         "dec_map_kernel": 13 * m}
@@ -166,7 +166,7 @@ def run_simplify(mesh, voxel, origin):
                          "output": {"vertices": kv, "faces": kf, "faces_kept_share": kf / max(n, 1)},
                          "cluster_table": {"slots": slots, "load_factor": K / slots, "mean_probe_length": probed.weld_probes / max(m, 1)},
                          "kernels": per_kernel(kernel_times(lambda: mesh.decimate(cell, origin)), kernel_bytes),
-                         "note": "weld_insert_kernel / dec_rep_kernel run twice (cells, then sorted triples): their times are the "
+                         "note": "weld_insert_kernel / weld_rep_kernel run twice (cells, then sorted triples): their times are the "
                                  "sums, their bytes those of the vertex pass"}
     adj = mesh.vertex_faces()
     mesh.vertex_normals(adj)

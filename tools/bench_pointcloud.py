@@ -128,7 +128,7 @@ def main():
     faster = all(r["device_s"] < r["host_s"] for r in rounds)
     nblk = -(-P // PC_THREADS)
     rows_per_view = n / VIEWS                              # mean over the views: a launch's share of the stored rows
-    need = (("pc_count_kernel", 4 * P + 8 * nblk), ("pc_scan_kernel", None),
+    need = (("pc_count_kernel", 4 * P + 8 * nblk), ("scan_sums_kernel", None),
             ("pc_scatter_kernel", int(4 * P + 8 * nblk + 24 * rows_per_view)), ("pc_bounds_kernel", 24 * n),
             ("pc_bounds_final_kernel", None))
     kernels = kernel_table(lambda: device_side(pc, cams, depths, origin), need)
