@@ -1017,6 +1017,73 @@ int sfgs_mesh_vertex_faces(const int32_t* faces, int64_t n, int64_t m, int32_t* 
 int sfgs_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t m, int64_t n, const int32_t* offsets,
                              const int32_t* records, float* normals, long long* state, void* stream);
 
+/* ---- Mesh rendering (added under ABI 28: new symbols only; csrc/mesh_raster.hip, csrc/mesh_raster_math.h; Python: Mesh.render):
+ * the mesh seen from a camera -- depth along the forward axis, the index of the visible face, its normal and its colour per
+ * pixel. tests/mesh_render_np.py states the result in numpy and the kernels equal it byte for byte, run after run: coverage is
+ * decided in integers and a pixel's winner by an integer minimum, so neither the order of arrival nor the route of a face
+ * (small_max) nor the launch shape changes a byte. Float64 arithmetic is one rounded operation at a time, in the order written.
+ *   1. VERTEX. p = float64 of the float32 position; q = p - c; cam[a] = (q0 M[3a] + q1 M[3a+1]) + q2 M[3a+2]; z = cam[2];
+ *      u = cam[0] focal_x / z + cx_pix, v = cam[1] focal_y / z + cy_pix (geo_project's sequence; M, c as in SfgsTsdfView; pixel
+ *      centres sit at integer (col, row)). X = rint(256 u), Y = rint(256 v), ties to even. A vertex is UNUSABLE when u, v or z
+ *      is not finite, when z <= near, or when |X| or |Y| exceeds 2^28. A face with an unusable vertex (or with an index outside
+ *      0 ... m - 1, which also raises status bit 3) is not drawn and counts as CLIPPED. There is NO near-plane clipping: a face
+ *      that crosses the plane z = near disappears as a whole.
+ *   2. FACE (a, b, c). As = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) in int64 (every product < 2^59). As == 0, two equal indices
+ *      included: not drawn, DEGENERATE. With sigma = the sign of focal_x focal_y det(M) (det = (M0 (M4 M8 - M5 M7) - M1 (M3 M8 -
+ *      M5 M6)) + M2 (M3 M7 - M4 M6)), the normal (b - a) x (c - a) points toward the camera exactly when sigma As < 0: in the
+ *      camera's frame n . a = det[a b c], and the screen area has the sign of det[a b c] focal_x focal_y / (za zb zc). That is the
+ *      outward, free side of sfgs_tsdf_extract's winding. cull == 1: a face turned away is not drawn, CULLED. Every other face is DRAWN
+ *      (whether or not it covers a pixel). sgn = the sign of As, A = |As|.
+ *   3. COVERAGE. The edge opposite corner i runs from corner j = i + 1 to k = i + 2 (mod 3): (dx, dy) = sgn (Xk - Xj, Yk - Yj),
+ *      E_i(col, row) = dx (256 row - Yj) - dy (256 col - Xj), so that E_0 + E_1 + E_2 = A and the inside is positive. Pixel (col, row)
+ *      is covered when every E_i > 0, or E_i == 0 and (dy < 0 or (dy == 0 and dx > 0)): a zero belongs to left and top edges. The
+ *      rule reads the direction alone and answers the two directions of an edge differently, so a pixel centre on an edge shared by
+ *      two faces belongs to exactly one of them, one on a shared vertex to at most one of the fan. Only pixels of the image inside
+ *      the box ceil(min X / 256) ... floor(max X / 256) (and Y) are tested; no other can be covered.
+ *   4. DEPTH. q_i = (double)E_i / z_i, s = (q0 + q1) + q2, depth = (float)((double)A / s). The pixel is kept when depth > 0 and
+ *      (double)depth <= far.
+ *   5. WINNER. The minimum over the kept faces of the key (float32 depth bits << 32) | face index: the nearest face, of equal
+ *      depths the smaller index. A pixel nothing covers: depth 0, face -1, zeros in normal and rgb.
+ *   6. ATTRIBUTES of the winner. b_i = q_i / s; an attribute is (b0 a0 + b1 a1) + b2 a2 in float64 on the corners' float32
+ *      values. rgb = its float32. normal: with vertex_normals == NULL the face's flat normal -- N = (b - a) x (c - a) as in
+ *      VERTEX_NORMALS above, winding as stored, not turned toward the camera; with vertex_normals (float32 [m][3]) N = the
+ *      interpolated attribute, kept in float64; either way float32(N / len), len = sqrt((Nx Nx + Ny Ny) + Nz Nz), or (0, 0, 0)
+ *      unless len is finite and > 0.
+ *   depth float32 [H][W]; face int32 [H][W]; normal float32 [3][H][W] or NULL; rgb float32 [3][H][W], NULL exactly when colors is.
+ *   state: EIGHT int64 words on the device, rewritten by every call: 0 ... 3 = the faces DRAWN, CULLED, CLIPPED, DEGENERATE (they
+ *   sum to n), 4 = a status (bit 3: a face index out of range; bit 0: a list of larger faces was asked for more than its n entries
+ *   -- a face is appended at most once, so this is never raised; it exists so that a broken invariant is reported, not a face
+ *   dropped in silence), 5 ... 7 zero.
+ *   small_max: a face whose clipped box holds at most this many pixels is rasterised by its own thread, a larger one by waves
+ *   over 8 x 8 tiles; -1 = the library's default. The routes give the same bytes. Mechanism: four kernels (project, faces, large
+ *   faces, resolve), relaxed agent-scope atomicMin on 64-bit keys in `scratch`, no float atomics; the two lists of larger faces
+ *   (up to 64 tiles: a wave per face; beyond: 256 waves per face) hold n entries each and a face is appended at most once, so
+ *   they cannot overflow; their lengths stay on the device.
+ * Refusals are SFGS_E_ARG, made before any GPU work: a NULL pointer, a wrong struct_size, m or n out of range, faces over no
+ * vertex, H or W < 1, H W > 2^30, a non-finite M, c or principal point, a focal length that is zero or not finite, near < 0 or not
+ * finite, far <= near or NaN, an unknown cull, small_max outside -1 ... 2^30, rgb that does not go with colors, vertex_normals
+ * without normal, a scratch too small. No profiler ids. */
+typedef struct SfgsMeshRender {
+  uint32_t struct_size;          /* = sizeof(SfgsMeshRender) */
+  int32_t H, W;
+  int32_t cull;                  /* 0: draw both sides; 1: do not draw faces turned away */
+  double M[9];                   /* world = cam @ M + c */
+  double c[3];
+  double cx_pix, cy_pix, focal_x, focal_y, near, far;
+  int64_t m, n, small_max;
+  const float* vertices;         /* device, [m][3] */
+  const float* colors;           /* device, [m][3], or NULL */
+  const int32_t* faces;          /* device, [n][3] */
+  const float* vertex_normals;   /* device, [m][3], or NULL: the flat normal */
+  float* depth;                  /* device, [H][W] */
+  int32_t* face;                 /* device, [H][W] */
+  float* normal;                 /* device, [3][H][W], or NULL */
+  float* rgb;                    /* device, [3][H][W]; NULL exactly when colors is */
+  long long* state;              /* device, [8] */
+} SfgsMeshRender;
+size_t sfgs_mesh_render_scratch_bytes(int64_t m, int64_t n, int32_t H, int32_t W);      /* 0: bad arguments */
+int sfgs_mesh_render(const SfgsMeshRender* args, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the
  * per-pixel tests, before the pixel saturated -- with blend weight w = alpha T:

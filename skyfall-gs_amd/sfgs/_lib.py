@@ -176,6 +176,14 @@ class SfgsTsdfRay(C.Structure):
                 ("rgb", C.c_void_p)]
 
 
+class SfgsMeshRender(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("cull", C.c_int32), ("M", C.c_double * 9),
+                ("c", C.c_double * 3), ("cx_pix", C.c_double), ("cy_pix", C.c_double), ("focal_x", C.c_double), ("focal_y", C.c_double),
+                ("near", C.c_double), ("far", C.c_double), ("m", C.c_int64), ("n", C.c_int64), ("small_max", C.c_int64),
+                ("vertices", C.c_void_p), ("colors", C.c_void_p), ("faces", C.c_void_p), ("vertex_normals", C.c_void_p),
+                ("depth", C.c_void_p), ("face", C.c_void_p), ("normal", C.c_void_p), ("rgb", C.c_void_p), ("state", C.c_void_p)]
+
+
 class SfgsConsistencyArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("ref", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("min_views", C.c_int32), ("table", C.c_void_p), ("rel_tol", C.c_double), ("px_tol2", C.c_double)]
@@ -277,6 +285,8 @@ SYMBOLS = {
     "sfgs_mesh_vertex_faces_scratch_bytes": (_SZ, [_I64]),
     "sfgs_mesh_vertex_faces": (C.c_int, [_V, _I64, _I64, _V, _V, _V, _V, _SZ, _V]),
     "sfgs_mesh_vertex_normals": (C.c_int, [_V, _V, _I64, _I64, _V, _V, _V, _V, _V]),
+    "sfgs_mesh_render_scratch_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
+    "sfgs_mesh_render": (C.c_int, [C.POINTER(SfgsMeshRender), _V, _SZ, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

@@ -32,7 +32,21 @@ vertex keeps that vertex's bytes), maps the faces through the cells and drops th
 face's set of three vertices (drop_duplicates) and then every cell no face is left on. A vertex whose cell is not finite or
 leaves int32 is bad: it joins no cell, its faces go, and the result's first sized use raises ValueError.
 
+Render (csrc/mesh_raster.hip; include/sfgs.h in words, tests/mesh_render_np.py in numpy; byte for byte as well):
+
+    view = small.render(camera, 1024, 1024, normals=normals, cull="back")   # MeshView: depth [1,H,W], face [H,W], normal, rgb
+    drawn, culled, clipped, degenerate = view.check()                       # ONE host read
+
+Every vertex is projected in float64 and snapped to 1/256 pixel; coverage is decided by int64 edge functions with a top-left
+rule (a pixel centre on an edge two faces share belongs to exactly one of them), depth is interpolated perspective-correctly
+and rounded to float32, and a pixel goes to the smallest (depth bits, face index): no order of arrival changes a byte. The
+rendered depth is an ordinary view, as a ray-cast one is: it goes into add_views, evaluate_dsm, sfgs.pointcloud, sfgs.ortho
+and ViewSet. There is NO near-plane clipping: a face with a vertex at or in front of `near` (or beyond 2^20 pixels from the
+image's origin, or not finite) is not drawn as a whole and counted as clipped -- keep the camera outside the mesh's
+triangles, or expect holes where they cross the camera's plane. No anti-aliasing, no textures.
+
 There is no hole filling or smoothing, and no torch fallback: without the HIP library every operator raises."""
+import math
 import os
 
 import numpy as np
@@ -40,9 +54,10 @@ import torch
 
 from . import _call
 from . import _lib as L
-from .geometry import _vec
+from .geometry import _check_view, _vec
+from .tsdf import _positive
 
-__all__ = ["Mesh", "Components", "VertexFaces", "weld", "MAX_TRIANGLES"]
+__all__ = ["Mesh", "Components", "VertexFaces", "MeshView", "weld", "MAX_TRIANGLES"]
 
 MAX_TRIANGLES = 1 << 29
 _INT32_MAX = int(np.iinfo(np.int32).max)
@@ -126,6 +141,28 @@ class VertexFaces(tuple):
         status = int(self._state[2])
         _raise_status(status, "vertex_faces")
         return status
+
+
+class MeshView:
+    """The result of Mesh.render, on the device. depth: float32 [1,H,W], 0 where no face covers the pixel; face: int32 [H,W], the
+    index of the visible face, -1 where none; normal: float32 [3,H,W] in the world frame, zeros where depth is 0, or None; rgb:
+    float32 [3,H,W], zeros where depth is 0, or None when the mesh has no colours; counts: int64 [4], the faces drawn, culled,
+    clipped (a vertex unusable: not finite, at or in front of near, beyond the guard band) and degenerate (zero area after the
+    snap). An ordinary view: depth goes into add_views, evaluate_dsm, sfgs.pointcloud, sfgs.ortho and ViewSet."""
+
+    def __init__(self, depth, face, normal, rgb, state):
+        self.depth, self.face, self.normal, self.rgb, self._state = depth, face, normal, rgb, state
+
+    @property
+    def counts(self):
+        """int64 [4] on the device: drawn, culled, clipped, degenerate"""
+        return self._state[:4]
+
+    def check(self):
+        """ONE host read: raises if the kernels left a status; -> (drawn, culled, clipped, degenerate) as ints."""
+        words = self._state.tolist()
+        _raise_status(words[4], "render")
+        return tuple(words[:4])
 
 
 class Mesh:
@@ -318,6 +355,82 @@ class Mesh:
             L.check(lib.sfgs_mesh_vertex_normals(L.ptr(self.vertex_buffer), L.ptr(self.face_buffer), m, n, L.ptr(adj.offsets),
                                                  L.ptr(adj.records), L.ptr(normals), L.ptr(adj._state), _call.stream(dev)))
         return normals
+
+    def render(self, camera, height, width, near=0.0, far=math.inf, normals=True, cull=None, out=None, _small_max=None):
+        """-> MeshView: the mesh seen from `camera` at height x width pixels -- depth along the forward axis (0 where no face
+        covers the pixel), the index of the visible face (-1), its normal in the world frame and, when the mesh has colours, the
+        interpolated colour -- with four launches and nothing read back beyond this mesh's own sizes. camera: read as
+        TsdfVolume.raycast reads one (R, T, focal_x, focal_y; cx, cy default to 0). near, far: a face with a vertex at or in
+        front of `near` is not drawn (there is no near-plane clipping), a pixel deeper than `far` is not kept. normals: True =
+        the visible face's flat normal (winding as stored), a float32 [m,3] tensor on the mesh's device (vertex_normals()) = the
+        interpolated vertex normals, False = none. cull: None draws both sides, "back" only the faces whose normal points
+        toward the camera. out: a MeshView of an earlier call with the same arguments, written again in place.
+        _small_max: private; the box size in pixels up to which a face is rasterised by its own thread (every value gives the
+        same bytes)."""
+        for name, v in (("height", height), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        H, W = int(height), int(width)
+        if H * W > 1 << 30:
+            raise ValueError(f"height * width must not exceed 2^30, got {H} x {W}")
+        near = _positive(near, "near", at_least=0.0)
+        far = _positive(far, "far", allow_inf=True)
+        if not far > near:
+            raise ValueError(f"far must be above near, got near {near}, far {far}")
+        if cull not in (None, "back"):
+            raise ValueError(f"cull must be None or 'back', got {cull!r}")
+        if _small_max is not None and (isinstance(_small_max, bool) or not isinstance(_small_max, (int, np.integer)) or
+                                       not 0 <= _small_max <= 1 << 30):
+            raise ValueError(f"_small_max must be None or an integer in 0 ... 2^30, got {_small_max!r}")
+        rows = int(self.vertex_buffer.shape[0])
+        vnormals = None
+        if isinstance(normals, torch.Tensor):
+            vnormals = normals
+            _call.check_tensor("normals", vnormals, "[m,3]", lambda t: t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous())
+            _call.check_gpu(normals=vnormals)
+            _call.same_device(self.device, "the mesh's device", normals=vnormals)
+        elif not isinstance(normals, (bool, np.bool_)):
+            raise ValueError(f"normals must be a bool or a float32 [m,3] tensor, got {normals!r}")
+        want_normal, colours = vnormals is not None or bool(normals), self.color_buffer is not None
+        if out is not None:
+            if not isinstance(out, MeshView):
+                raise ValueError(f"out must be a MeshView, got {out!r}")
+            if (out.normal is not None) != want_normal or (out.rgb is not None) != colours:
+                raise ValueError("out was made with other normals or by a mesh with other colours")
+            _call.check_tensor("out.depth", out.depth, f"[1,{H},{W}]", lambda t: tuple(t.shape) == (1, H, W) and t.is_contiguous())
+            _call.check_tensor("out.face", out.face, f"[{H},{W}]", lambda t: tuple(t.shape) == (H, W) and t.is_contiguous(),
+                               dtypes=(torch.int32,))
+            for name, t in (("out.normal", out.normal), ("out.rgb", out.rgb)):
+                _call.check_tensor(name, t, f"[3,{H},{W}]", lambda t: tuple(t.shape) == (3, H, W) and t.is_contiguous(), none_ok=True)
+            _call.check_tensor("out state", out._state, "[8]", lambda t: tuple(t.shape) == (8,), dtypes=(torch.int64,))
+        try:
+            cam = (camera.R, camera.T, camera.focal_x, camera.focal_y, getattr(camera, "cx", 0.0), getattr(camera, "cy", 0.0))
+        except AttributeError as e:
+            raise ValueError(f"camera: {e}") from None
+        dev = self.device
+        view = out
+        if view is None:
+            view = MeshView(torch.empty((1, H, W), dtype=torch.float32, device=dev), torch.empty((H, W), dtype=torch.int32, device=dev),
+                            torch.empty((3, H, W), dtype=torch.float32, device=dev) if want_normal else None,
+                            torch.empty((3, H, W), dtype=torch.float32, device=dev) if colours else None,
+                            torch.empty(8, dtype=torch.int64, device=dev))
+        # the view's checks on the depth map that will be written: its size, its device, the camera's numbers
+        _, _, (M, c, _, cx_pix, cy_pix, fx, fy) = _check_view(dev, view.depth, *cam, None, None, centre_from_view=True, face=view.face,
+                                                              normal=view.normal, rgb=view.rgb, state=view._state)
+        m, n = self._sizes()
+        if vnormals is not None and int(vnormals.shape[0]) not in (m, rows):
+            raise ValueError(f"normals must have a row per vertex ({m}), got {int(vnormals.shape[0])}")
+        lib = L.load()
+        args = L.SfgsMeshRender(L.C.sizeof(L.SfgsMeshRender), H, W, 0 if cull is None else 1, M, c, cx_pix, cy_pix, fx, fy, near, far,
+                                m, n, -1 if _small_max is None else int(_small_max), self.vertex_buffer.data_ptr(),
+                                None if not colours else self.color_buffer.data_ptr(), self.face_buffer.data_ptr(),
+                                None if vnormals is None else vnormals.data_ptr(), view.depth.data_ptr(), view.face.data_ptr(),
+                                None if view.normal is None else view.normal.data_ptr(),
+                                None if view.rgb is None else view.rgb.data_ptr(), view._state.data_ptr())
+        with torch.cuda.device(dev):
+            scratch = _call.scratch(lib.sfgs_mesh_render_scratch_bytes(m, n, H, W), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_render(L.C.byref(args), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+        return view
 
     def save_ply(self, path, origin=None, normals=None):
         """Binary little-endian PLY in TriangleSoup.save_ply's layout: a `vertex` and a `face` element (`property list uchar int
