@@ -353,7 +353,8 @@ int sfgs_raster_forward_render(const SfgsFrame* frame, int32_t N, const void* ge
  * fully overwritten. Deterministic (no float atomics). Asynchronous. Writes one word of the `tiles` header: whether this
  * frame's dead list entries (behind their tile's last contributor) are skipped through the flags or receive zero records
  * one by one; decided per frame on the device, sfgs_set_option("prefill", "always" | "never") forces either path for
- * tests: the gradients are bit-identical. */
+ * tests: the gradients are bit-identical. With num_duplicates == 0 `dupgrad` may be NULL or of any size: nothing is read from it
+ * or written to it, whatever the option says. */
 int sfgs_raster_backward(const SfgsFrame* frame, const SfgsGaussians* g, const int32_t* radii,
                          const void* geom, const void* tiles, const void* bins, int64_t dup_capacity,
                          int64_t coarse_capacity, int64_t num_duplicates, const void* image, const float* dL_dcolor,

@@ -412,6 +412,9 @@ loss_final_kernel(const float* __restrict__ ssim_partials, const float* __restri
   }
   if (n_depth > 0) {
     const double n = S[DS_N];
+    // loss_depth_bwd_kernel loads every coefficient, whichever route it takes: the words this route does not use are
+    // zeros, not whatever the scratch held
+    for (int k = 0; k < CF_COUNT; ++k) coef[k] = 0.0;
     if (depth_is_l1) {
       ll1 = S[DS_ABS] / n;
       coef[CF_INV_N] = 1.0 / n;

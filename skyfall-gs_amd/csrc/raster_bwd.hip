@@ -428,14 +428,19 @@ extern "C" int sfgs_raster_backward(const SfgsFrame* frame, const SfgsGaussians*
   // the live flags behind the records (sfgs_internal.h: dupgrad_bytes). Without the prefill kernel its decision word keeps
   // the plan's zero -- or an EARLIER backward's decision over the same forward state: the readers then get no flag pointer
   // and composite_bwd writes the zero records itself
+  // A frame without duplicates owes no dupgrad blob at all (the checks above: it may be NULL or a dummy of any size), so
+  // nothing may be stored behind `dupgrad`: the prefill kernel still publishes its decision -- a forced "no", whatever the
+  // option or stale tile_dead counts say -- and neither it nor the readers are given a pointer into the blob
   const bool no_prefill = (frame->launch_hints & SFGS_HINT_NO_PREFILL) != 0;
-  uint8_t* live = (uint8_t*)dupgrad + dupgrad_flags_offset(dup_capacity);
+  const bool no_dups = num_duplicates == 0;
+  uint8_t* live = no_dups ? nullptr : (uint8_t*)dupgrad + dupgrad_flags_offset(dup_capacity);
+  uint4* zero_line = no_dups ? nullptr : (uint4*)((char*)dupgrad + dupgrad_zero_offset(dup_capacity));
   const uint8_t* live_r = no_prefill ? nullptr : live;
   const size_t zero_f4 = dupgrad_zero_offset(dup_capacity) / 16;
   { ProfScope ps_(KID_COMPOSITE_BWD, stream);
     if (!no_prefill)
     hipLaunchKernelGGL(dupgrad_prefill_kernel, dim3(512), dim3(256), 0, stream, TX8 * TY8, iv.tile_dead,
-                       (unsigned long long)num_duplicates, prefill_mode(), (uint4*)live, (uint4*)((char*)dupgrad + dupgrad_zero_offset(dup_capacity)), tv.hdr,
+                       (unsigned long long)num_duplicates, no_dups ? 2 : prefill_mode(), (uint4*)live, zero_line, tv.hdr,
                        (unsigned long long*)frame->feedback, (const unsigned long long*)tv.dup_pool,
                        (unsigned long long)dup_capacity, dup_pools_used(pre_blocks(N)));
     launch_composite_bwd(composite_grid(SX, SY, BE * BE / BWG_WAVES), stream, kf, TX8, TY8, SX, SY, tv.tile_range, bv.sorted_id,

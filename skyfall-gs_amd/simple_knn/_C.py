@@ -22,5 +22,6 @@ def distCUDA2(points):
     nbytes = int(lib.sfgs_knn_scratch_bytes(N))     # 0 for small clouds (brute force); the spatial path sorts into scratch
     scratch = _call.scratch(nbytes, dev) if nbytes else None
     with torch.cuda.device(dev):
-        L.check(lib.sfgs_knn_dist2(L.ptr(pts), N, L.ptr(out), L.ptr(scratch), nbytes, _call.stream(dev)))
+        L.check(lib.sfgs_knn_dist2(L.ptr(pts), N, L.ptr(out), L.ptr(scratch), scratch.numel() if nbytes else 0,
+                                  _call.stream(dev)))
     return out
