@@ -1085,6 +1085,97 @@ typedef struct SfgsMeshRender {
 size_t sfgs_mesh_render_scratch_bytes(int64_t m, int64_t n, int32_t H, int32_t W);      /* 0: bad arguments */
 int sfgs_mesh_render(const SfgsMeshRender* args, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Mesh queries (added under ABI 28: new symbols only; csrc/mesh_query.hip, csrc/mesh_query_math.h; Python: Mesh.face_grid,
+ * Mesh.closest, Mesh.sample): a uniform grid over the faces, the closest face of a point, points on the surface. The reference
+ * has no mesh step; tests/mesh_query_np.py states the results in numpy and the kernels equal it byte for byte. Float64 arithmetic
+ * is one rounded operation at a time, in the order written.
+ *   CELL. The cell of a coordinate x on an axis is floor((x - origin) / cell) in float64, for the vertices of a face and for a
+ *     query point alike. The function is monotone in x.
+ *   GRID, sfgs_mesh_grid_count then sfgs_mesh_grid_fill with the same struct and the same scratch. nx x ny x nz cells, cell
+ *     (x, y, z) has the index (z ny + y) nx + x. A face is LEFT OUT when one of its indices lies outside 0 ... m - 1 or one of its
+ *     nine coordinates is not finite. Every other face has, per axis, the range of cells from that of its smallest to that of its
+ *     largest coordinate, both clamped into 0 ... dim - 1. A face whose range holds more than max_cells cells (-1: the default,
+ *     4096) is LARGE: it goes to the large list (int32 [n], in no particular order; a face is appended at most once, so the list
+ *     cannot overflow) and every query tests it. Every other face is registered in every cell of its range: cell_start int32
+ *     [cells + 1] is the exclusive prefix sum of the cells' counts, pairs int32 [capacity] holds the face indices of cell c at
+ *     cell_start[c] ... cell_start[c + 1], ASCENDING. max_cells bounds the fill loop of any thread; 0 puts every face on the
+ *     large list, 2^30 none. state: FOUR int64 words, cleared by _count: 0 = the pairs in all (the capacity needed), 1 = the
+ *     length of the large list, 2 = a status, 3 = the faces left out. Status bit 5 (32): capacity < word 0, pairs beyond it
+ *     were not written and the table is not valid; bit 6 (64): more than 2^31 - 1 pairs; bit 3: a run outside the table; bit 1:
+ *     the segment sort reached its trip bound; bit 0: the large list was asked for more than n entries (never).
+ *     _count reads neither pairs nor capacity: a caller may read word 0 between the two calls and size pairs by it.
+ *     Mechanism: integer-atomic counts, an exclusive scan (three launches), a fill through atomic cursors, the segment sort of
+ *     VERTEX_FACES with a thread per cell.
+ *   CLOSEST, sfgs_mesh_closest over a FILLED grid. points: float32 or float64 [k][3] (points_f64), taken to float64. For each point
+ *     the answer is the minimum over all faces not left out of (d2, face index): d2 is the float64 squared distance to the
+ *     closed triangle by ONE function (mq_closest in csrc/mesh_query_math.h): with ab = b - a, ac = c - a, bc = c - b, ap, bp, cp
+ *     = p - a, p - b, p - c, dot(u, v) = (u0 v0 + u1 v1) + u2 v2, d1 ... d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp),
+ *     dot(ab, cp), dot(ac, cp), vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, the first of these that holds decides:
+ *       d1 <= 0 and d2 <= 0: a;  d3 >= 0 and d4 <= d3: b;  vc <= 0, d1 >= 0, d3 <= 0: a + (d1 / (d1 - d3)) ab;
+ *       d6 >= 0 and d5 <= d6: c;  vb <= 0, d2 >= 0, d6 <= 0: a + (d2 / (d2 - d6)) ac;
+ *       va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) bc;
+ *       else with s = (va + vb) + vc: (a + (vb / s) ab) + (vc / s) ac;
+ *     a quotient whose denominator is not > 0 is taken as 0; d2 = dot(p - q, p - q). A d2 that is not finite never wins, equal d2
+ *     goes to the smaller face index. An answer with d2 > max_distance max_distance (max_distance >= 0, +inf: none), a point with a
+ *     coordinate that is not finite and a point without any face get face -1, sqdist +inf and closest (0, 0, 0). sqdist float64
+ *     [k], face int32 [k], closest float32 [k][3] or NULL (q rounded once). state: FOUR int64 words: 0 = the queries answered,
+ *     1 = those without a face, 2 = a status (bit 3: a table entry out of range), 3 = the grid's faces left out.
+ *     The grid does not change a byte of this. Search: the large list in full, then the Chebyshev rings of cells around the
+ *     query's own cell (clamped to +-2^30, which only brings it nearer), from the first ring r0 that holds a cell of the grid,
+ *     intersected with the grid. After ring r the search stops when best d2 < (r cell)^2 (1 - 2^-20), or when
+ *     r cell (1 - 2^-20) > max_distance, at the latest after the ring of the grid's farthest cell, which is at most r0 + the
+ *     largest dimension - 1. Exact because, from ring r0 on, a face registered in no visited cell has a coordinate whose cell
+ *     differs from the query's by more than r on some axis (a range is clamped only toward cells that were visited), and CELL
+ *     is monotone and shared: that coordinate is at least r cell (1 - 2^-40) away; the margin covers the rounding of the
+ *     quotients and of d2. The rule does not hold below r0: a face outside the grid sits in a border cell, however near a
+ *     query outside the grid it is.
+ *     One thread per query, its result written by that thread alone; no float atomics, no atomics on the outputs.
+ *   SAMPLE, sfgs_mesh_sample. Face t with positions a, b, c has the area A = 0.5 sqrt(dot(N, N)), N as in VERTEX_NORMALS, and
+ *     e = A density. mix(seed, t, j) = f(f(f(seed ^ 0x9e3779b9) ^ t 0x7feb352d) ^ j 0x846ca68b) in uint32 arithmetic with f =
+ *     murmur3's 32-bit finaliser; unit(h) = (h + 0.5) / 2^32. The face gets floor(e) + (unit(mix(seed, t, 2^32 - 1)) < e -
+ *     floor(e)) samples. Sample j: u1, u2 = unit(mix(seed, t, 2 j)), unit(mix(seed, t, 2 j + 1)), both replaced by 1 - u when
+ *     u1 + u2 > 1; a component of its position (and, with colours, of its colour) is float32((a + u1 (b - a)) + u2 (c - a)) in
+ *     float64. Rows are ordered by face, then j. A face with an index out of range samples nothing (status bit 3); so does one
+ *     whose e is not finite or whose count exceeds 2^20 (status bit 7, 128). points float32 [capacity][3], face int32
+ *     [capacity], colors_out float32 [capacity][3] or NULL; a row at or beyond capacity is not written but still counted.
+ *     state: FOUR int64 words: 0 = the samples found, 2 = the status (bit 6: more than 2^31 - 1 samples). capacity 0 only counts.
+ * Refusals are SFGS_E_ARG, made before any GPU work: a NULL pointer, a wrong struct_size, m or n out of range, faces over no
+ * vertex, a dimension < 1 or more than 2^28 cells, a cell that is not finite and positive, an origin that is not finite, max_cells
+ * outside -1 ... 2^30, a capacity outside 0 ... 2^31 - 1, a negative or NaN max_distance or density, a scratch too small. No
+ * profiler ids. */
+typedef struct SfgsMeshGrid {
+  uint32_t struct_size;          /* = sizeof(SfgsMeshGrid) */
+  int32_t nx, ny, nz;
+  double origin[3], cell;
+  int64_t m, n, max_cells, capacity;
+  const float* vertices;         /* device, [m][3] */
+  const int32_t* faces;          /* device, [n][3] */
+  int32_t* cell_start;           /* device, [nx ny nz + 1] */
+  int32_t* pairs;                /* device, [capacity]; not read by _count */
+  int32_t* large;                /* device, [n] */
+  long long* state;              /* device, [4] */
+} SfgsMeshGrid;
+size_t sfgs_mesh_grid_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);                 /* 0: bad arguments */
+int sfgs_mesh_grid_count(const SfgsMeshGrid* grid, void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_mesh_grid_fill(const SfgsMeshGrid* grid, void* scratch, size_t scratch_bytes, void* stream);
+int sfgs_mesh_closest(const SfgsMeshGrid* grid, const void* points, int32_t points_f64, int64_t k, double max_distance, double* sqdist,
+                      int32_t* face, float* closest, long long* state, void* stream);
+/* SUMMARY, sfgs_mesh_distance_summary, of a CLOSEST result: over the ANSWERED queries (face >= 0), with d = sqrt(sqdist) in float64.
+ *   out: TWENTY int64 words, rewritten by every call: 0 ... 2 = the bits of three float64 -- the sum of d, the sum of sqdist, the
+ *   largest d (0 without an answer); 3 = the queries answered; 4 + j = those with d <= thresholds[j] (j < num_thresholds <= 16,
+ *   thresholds: HOST doubles >= 0), the rest zero. The counts are integers and exact. The sums are formed in a fixed order: the
+ *   workgroup of queries 4096 b ... 4096 b + 4095 adds, per thread t, its items t, t + 256, ... in that order from +0.0, then
+ *   the 256 threads' values in a binary tree (s = 128, 64, ..., 1: value[t] += value[t + s]); the workgroups' sums are added the
+ *   same way, thread t taking workgroups t, t + 256, ...: the same bytes run after run. One launch; the last workgroup to
+ *   finish (an integer ticket in `scratch`) adds the partials. No float atomics. */
+size_t sfgs_mesh_distance_summary_scratch_bytes(int64_t k);            /* 0: bad arguments */
+int sfgs_mesh_distance_summary(const double* sqdist, const int32_t* face, int64_t k, const double* thresholds, int32_t num_thresholds,
+                               long long* out, void* scratch, size_t scratch_bytes, void* stream);
+size_t sfgs_mesh_sample_scratch_bytes(int64_t n);                      /* 0: bad arguments */
+int sfgs_mesh_sample(const float* vertices, const float* colors, const int32_t* faces, int64_t m, int64_t n, double density,
+                     uint32_t seed, int64_t capacity, float* points, int32_t* face, float* colors_out, long long* state, void* scratch,
+                     size_t scratch_bytes, void* stream);
+
 /* ---- Per-Gaussian blend-weight statistics (ABI 28; csrc/importance.hip; Python: sfgs.importance): which Gaussians of a scene
  * show up in a set of views, and how much. For every (pixel, Gaussian) pair that the forward BLENDED -- accepted by the
  * per-pixel tests, before the pixel saturated -- with blend weight w = alpha T:

@@ -184,6 +184,13 @@ class SfgsMeshRender(C.Structure):
                 ("depth", C.c_void_p), ("face", C.c_void_p), ("normal", C.c_void_p), ("rgb", C.c_void_p), ("state", C.c_void_p)]
 
 
+class SfgsMeshGrid(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_double * 3),
+                ("cell", C.c_double), ("m", C.c_int64), ("n", C.c_int64), ("max_cells", C.c_int64), ("capacity", C.c_int64),
+                ("vertices", C.c_void_p), ("faces", C.c_void_p), ("cell_start", C.c_void_p), ("pairs", C.c_void_p),
+                ("large", C.c_void_p), ("state", C.c_void_p)]
+
+
 class SfgsConsistencyArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("ref", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("min_views", C.c_int32), ("table", C.c_void_p), ("rel_tol", C.c_double), ("px_tol2", C.c_double)]
@@ -287,6 +294,14 @@ SYMBOLS = {
     "sfgs_mesh_vertex_normals": (C.c_int, [_V, _V, _I64, _I64, _V, _V, _V, _V, _V]),
     "sfgs_mesh_render_scratch_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
     "sfgs_mesh_render": (C.c_int, [C.POINTER(SfgsMeshRender), _V, _SZ, _V]),
+    "sfgs_mesh_grid_scratch_bytes": (_SZ, [_I32, _I32, _I32]),
+    "sfgs_mesh_grid_count": (C.c_int, [C.POINTER(SfgsMeshGrid), _V, _SZ, _V]),
+    "sfgs_mesh_grid_fill": (C.c_int, [C.POINTER(SfgsMeshGrid), _V, _SZ, _V]),
+    "sfgs_mesh_closest": (C.c_int, [C.POINTER(SfgsMeshGrid), _V, _I32, _I64, C.c_double, _V, _V, _V, _V, _V]),
+    "sfgs_mesh_distance_summary_scratch_bytes": (_SZ, [_I64]),
+    "sfgs_mesh_distance_summary": (C.c_int, [_V, _V, _I64, C.POINTER(C.c_double), _I32, _V, _V, _SZ, _V]),
+    "sfgs_mesh_sample_scratch_bytes": (_SZ, [_I64]),
+    "sfgs_mesh_sample": (C.c_int, [_V, _V, _V, _I64, _I64, C.c_double, C.c_uint32, _I64, _V, _V, _V, _V, _V, _SZ, _V]),
     "sfgs_raster_blend_stats": (C.c_int, [C.POINTER(SfgsFrame), _I32, _V, _V, _V, _SZ, _I64, _I64, _V,
                                            C.POINTER(SfgsBlendStats), _V]),
     "sfgs_blend_stats_views": (C.c_int, [_I32, _V, _V, _V, _V]),

@@ -45,6 +45,29 @@ and ViewSet. There is NO near-plane clipping: a face with a vertex at or in fron
 image's origin, or not finite) is not drawn as a whole and counted as clipped -- keep the camera outside the mesh's
 triangles, or expect holes where they cross the camera's plane. No anti-aliasing, no textures.
 
+Queries (csrc/mesh_query.hip; include/sfgs.h in words, tests/mesh_query_np.py in numpy; byte for byte as well):
+
+    grid = clean.face_grid(cell=2 * voxel, origin=vol_origin, dims=(nx // 2, ny // 2, nz // 2))   # FaceGrid: a CSR table of faces per cell
+    d = clean.closest(points, grid, max_distance=4 * voxel)                  # MeshDistance: sqdist float64 [k], face int32 [k]
+    answered, without, left_out = d.check()                                  # ONE host read
+    pts = small.sample(density=1 / voxel ** 2, seed=0)                       # MeshSamples: points, face, colors, uniform per area
+    error = clean.closest(pts.points).distance                               # how far the decimated surface lies from the full one
+
+The cell of a coordinate is floor((x - origin) / cell) in float64, for faces and queries alike. A face is registered in every
+cell its box overlaps (clamped into the grid); one whose range holds more than 4096 cells goes to a large list that every query
+tests; one with an index out of range or a vertex that is not finite is left out and counted. closest answers, per point, the
+minimum over all faces not left out of (squared distance to the closed triangle in float64, face index): it tests the large
+list, then the Chebyshev rings of cells around the point's own cell from the first that meets the grid, and stops after ring r
+once best < (r cell)^2 (1 - 2^-20) -- a face in no visited cell is at least r cell away, because the cell function is monotone
+and shared -- or r cell (1 - 2^-20) > max_distance. The grid changes no byte of the answer. One thread per query: a wave per
+query was measured (profiles/r27_mesh_distance_ab.txt: a quarter faster against the 4 M-face mesh, 3 - 5.5 x slower elsewhere)
+and is kept as tools/variants/mesh_query_wave.patch; bucketing the queries by cell was not built. Without a grid the cell is default_cell()'s: max(sqrt(S / n),
+L / 512), S half the surface of the bounds, L their longest side. sample gives face t floor(e) + (u < e - floor(e)) points, e =
+area x density, u and the positions from a 32-bit integer mixer of (seed, face, counter): the same bytes for the same seed.
+d.summary(thresholds) reduces a result in one launch and one host read: exact counts per threshold, mean, RMS and max from
+float64 sums formed in a fixed order (the same bytes run after run); compare(a, b, density, max_distance, thresholds) samples
+both meshes, queries each one's samples against the other and gives the Chamfer distance, precision, recall and F-score. Timings: tools/bench_mesh_distance.py, profiles/r27_mesh_distance_ab.txt.
+
 There is no hole filling or smoothing, and no torch fallback: without the HIP library every operator raises."""
 import math
 import os
@@ -57,11 +80,15 @@ from . import _lib as L
 from .geometry import _check_view, _vec
 from .tsdf import _positive
 
-__all__ = ["Mesh", "Components", "VertexFaces", "MeshView", "weld", "MAX_TRIANGLES"]
+__all__ = ["Mesh", "Components", "VertexFaces", "MeshView", "FaceGrid", "MeshDistance", "MeshSamples", "DistanceSummary",
+           "MeshComparison", "weld", "compare", "grid_from_bounds", "default_cell", "MAX_TRIANGLES", "MAX_GRID_CELLS"]
 
 MAX_TRIANGLES = 1 << 29
+MAX_GRID_CELLS = 1 << 28
+MAX_THRESHOLDS = 16
 _INT32_MAX = int(np.iinfo(np.int32).max)
 _ST_BOUND, _ST_BAD_INDEX, _ST_BAD_VERTEX = 7, 8, 16
+_ST_CAPACITY, _ST_PAIRS, _ST_BAD_FACE = 32, 64, 128
 
 
 def _raise_status(status, what):
@@ -163,6 +190,192 @@ class MeshView:
         words = self._state.tolist()
         _raise_status(words[4], "render")
         return tuple(words[:4])
+
+
+def _raise_query_status(status, what, need=None, capacity=None):
+    if status & _ST_PAIRS:
+        raise ValueError(f"{what}: more than 2^31 - 1 entries ({need}); use a larger cell or a smaller density")
+    if status & _ST_CAPACITY:
+        raise ValueError(f"{what}: {need} (face, cell) pairs found, capacity {capacity}: the pairs beyond it were dropped and the "
+                         f"table is not valid; a capacity of {need} would have sufficed")
+    if status & _ST_BAD_FACE:
+        raise ValueError(f"{what}: a face has an area that is not finite, or more than 2^20 samples (it sampled nothing)")
+    _raise_status(status, what)
+
+
+def grid_from_bounds(box, cell):
+    """-> (origin float64 [3], dims): the face grid over the bounds `box` = (lo, hi): origin = lo, dims = floor((hi - lo) / cell)
+    + 1 per axis in float64; a mesh without a usable face (box None) gets one cell at the origin."""
+    if box is None:
+        return np.zeros(3), (1, 1, 1)
+    lo, hi = (np.asarray(b, dtype=np.float64) + 0.0 for b in box)           # + 0.0: a minimum of -0.0 and +0.0 is +0.0 either way
+    dims = tuple(int(d) for d in np.floor((hi - lo) / np.float64(cell)) + 1.0)
+    return lo, dims
+
+
+def default_cell(box, n):
+    """The cell Mesh.closest picks without a grid: max(sqrt(S / n), L / 512) with (ex, ey, ez) = the extent of the bounds, S =
+    ex ey + ey ez + ez ex (half the box's surface: a surface of n faces inside it then has about a face per cell it passes
+    through) and L the longest extent (at most 512^3 = 2^27 cells); 1 when that is not positive."""
+    if box is None or n < 1:
+        return 1.0
+    ex, ey, ez = (float(h) - float(l) for l, h in zip(*box))
+    cell = max(math.sqrt((ex * ey + ey * ez + ez * ex) / n), max(ex, ey, ez) / 512.0)
+    return cell if cell > 0.0 and math.isfinite(cell) else 1.0
+
+
+class FaceGrid:
+    """The result of Mesh.face_grid, on the device: a uniform grid over the faces as a CSR table. cell, origin (float64 [3]),
+    dims (nx, ny, nz); cell (x, y, z) has the index (z ny + y) nx + x. cell_start: int32 [nx ny nz + 1]; pairs: int32
+    [capacity], the faces of cell c at cell_start[c]:cell_start[c + 1], ascending; large: int32 [n], the faces whose cell range
+    was larger than max_cells, in no particular order (num_large of them), which every query tests."""
+
+    def __init__(self, mesh, cell, origin, dims, cell_start, pairs, large, state, args):
+        self.mesh, self.cell, self.origin, self.dims = mesh, cell, origin, dims
+        self.cell_start, self.pairs, self.large, self._state, self._args = cell_start, pairs, large, state, args
+
+    @property
+    def num_pairs(self):
+        """int64 [] on the device: the (face, cell) pairs in all -- the capacity needed"""
+        return self._state[0]
+
+    @property
+    def num_large(self):
+        """int64 [] on the device"""
+        return self._state[1]
+
+    @property
+    def skipped(self):
+        """int64 [] on the device: the faces left out (an index out of range, a coordinate that is not finite)"""
+        return self._state[3]
+
+    def check(self):
+        """ONE host read: raises if the capacity was too small (naming the number needed) or the kernels left another status;
+        -> (pairs, large, skipped) as ints."""
+        pairs, large, status, skipped = self._state.tolist()
+        _raise_query_status(status, "face_grid", pairs, int(self.pairs.shape[0]))
+        return pairs, large, skipped
+
+
+class MeshDistance:
+    """The result of Mesh.closest, on the device. sqdist: float64 [k], the squared distance to the closest face, +inf where
+    there is none; face: int32 [k], its index, -1 where none (no face at all, one beyond max_distance, a point that is not
+    finite); point: float32 [k,3], the closest point, or None; grid: the FaceGrid that was searched."""
+
+    def __init__(self, sqdist, face, point, state, grid):
+        self.sqdist, self.face, self.point, self._state, self.grid = sqdist, face, point, state, grid
+
+    @property
+    def counts(self):
+        """int64 [3] on the device: the queries answered, those without a face, the faces the grid left out"""
+        return self._state[[0, 1, 3]]
+
+    @property
+    def distance(self):
+        """float64 [k]: sqrt(sqdist)"""
+        return torch.sqrt(self.sqdist)
+
+    def check(self):
+        """ONE host read: raises if the kernel left a status; -> (answered, without a face, faces left out) as ints."""
+        answered, without, status, skipped = self._state.tolist()
+        _raise_query_status(status, "closest")
+        return answered, without, skipped
+
+    def summary(self, thresholds=()):
+        """-> DistanceSummary over the ANSWERED queries, d = sqrt(sqdist): one reduction launch and ONE host read. thresholds: up
+        to 16 numbers >= 0; per threshold the exact count of answered queries with d <= it. The sums of d and d^2 are float64,
+        formed in a fixed order (include/sfgs.h): the same bytes run after run."""
+        try:
+            taus = [float(t) for t in thresholds]
+        except (TypeError, ValueError):
+            raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
+        if len(taus) > MAX_THRESHOLDS or not all(t >= 0 for t in taus):
+            raise ValueError(f"thresholds must be at most {MAX_THRESHOLDS} numbers >= 0, got {thresholds!r}")
+        k, dev, lib = int(self.sqdist.shape[0]), self.sqdist.device, L.load()
+        with torch.cuda.device(dev):
+            out = torch.empty(4 + MAX_THRESHOLDS, dtype=torch.int64, device=dev)
+            scratch = _call.scratch(lib.sfgs_mesh_distance_summary_scratch_bytes(k), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_distance_summary(L.ptr(self.sqdist), L.ptr(self.face), k, (L.C.c_double * max(len(taus), 1))(*taus),
+                                                   len(taus), L.ptr(out), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+        words = np.array(out.tolist(), dtype=np.int64)              # ONE host read
+        sums = words[:3].view(np.float64)
+        return DistanceSummary(k, int(words[3]), float(sums[0]), float(sums[1]), float(sums[2]), tuple(taus),
+                               tuple(int(c) for c in words[4:4 + len(taus)]))
+
+
+class DistanceSummary:
+    """The result of MeshDistance.summary, on the host. queries; answered; sum_d, sum_d2, max: float64 over the answered queries;
+    thresholds and counts (answered queries with d <= threshold, exact). mean and rms are over the answered queries (NaN without
+    one); fractions are counts / QUERIES: a query without an answer is farther than every threshold."""
+
+    def __init__(self, queries, answered, sum_d, sum_d2, max_d, thresholds, counts):
+        self.queries, self.answered, self.sum_d, self.sum_d2, self.max = queries, answered, sum_d, sum_d2, max_d
+        self.thresholds, self.counts = thresholds, counts
+        self.mean = sum_d / answered if answered else math.nan
+        self.rms = math.sqrt(sum_d2 / answered) if answered else math.nan
+        self.fractions = tuple(c / queries if queries else math.nan for c in counts)
+
+
+class MeshComparison:
+    """The result of compare(a, b, ...): a_to_b / b_to_a: the DistanceSummary of a's samples against b and of b's against a;
+    chamfer: the mean of the two means; per threshold precision (a's samples within it of b), recall (b's within it of a) and
+    fscore = 2 P R / (P + R), 0 where both are 0."""
+
+    def __init__(self, a_to_b, b_to_a):
+        self.a_to_b, self.b_to_a = a_to_b, b_to_a
+        self.chamfer = 0.5 * (a_to_b.mean + b_to_a.mean)
+        self.precision, self.recall = a_to_b.fractions, b_to_a.fractions
+        self.fscore = tuple(2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(self.precision, self.recall))
+
+
+def compare(a, b, density, max_distance=None, thresholds=(), seed=0):
+    """-> MeshComparison of two meshes on one device: both are sampled at `density` (Mesh.sample with `seed`), each one's samples
+    are queried against the other (Mesh.closest with `max_distance`) and summarised (MeshDistance.summary with `thresholds`).
+    Plain Python over those three; it costs their host reads."""
+    if not isinstance(a, Mesh) or not isinstance(b, Mesh):
+        raise ValueError("compare takes two Mesh objects")
+    if a.device != b.device:
+        raise ValueError(f"the meshes must be on one device, got {a.device} and {b.device}")
+    pa, pb = a.sample(density, seed=seed, colors=False).points, b.sample(density, seed=seed, colors=False).points
+    return MeshComparison(b.closest(pa, max_distance=max_distance).summary(thresholds),
+                          a.closest(pb, max_distance=max_distance).summary(thresholds))
+
+
+class MeshSamples:
+    """The result of Mesh.sample, on the device. point_buffer float32 [capacity,3], face_buffer int32 [capacity], color_buffer
+    float32 [capacity,3] or None: rows at or beyond `count` never written; points / face / colors: the sized views (ONE host
+    read on first use, which raises when the capacity was too small or a face could not be sampled)."""
+
+    def __init__(self, points, face, colors, state, capacity):
+        self.point_buffer, self.face_buffer, self.color_buffer, self._state, self.capacity = points, face, colors, state, capacity
+        self._count_read = None
+
+    @property
+    def count(self):
+        """int64 [] on the device: the samples FOUND (more than `capacity` when the buffers were too small)"""
+        return self._state[0]
+
+    def _count(self):
+        if self._count_read is None:                      # ONE host read
+            k, _, status, _ = self._state.tolist()
+            _raise_query_status(status, "sample", k)
+            if k > self.capacity:
+                raise ValueError(f"MeshSamples: {k} samples found, capacity {self.capacity}: the rows beyond it were dropped; "
+                                 f"a capacity of {k} would have sufficed")
+            self._count_read = k
+        return self._count_read
+
+    @property
+    def points(self):
+        return self.point_buffer[:self._count()]
+
+    @property
+    def face(self):
+        return self.face_buffer[:self._count()]
+
+    @property
+    def colors(self):
+        return None if self.color_buffer is None else self.color_buffer[:self._count()]
 
 
 class Mesh:
@@ -431,6 +644,150 @@ class Mesh:
             scratch = _call.scratch(lib.sfgs_mesh_render_scratch_bytes(m, n, H, W), dev, refused_if_zero=True)
             L.check(lib.sfgs_mesh_render(L.C.byref(args), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
         return view
+
+    # ---- queries: the face grid, the closest face, points on the surface (csrc/mesh_query.hip) -------------------------------
+    def _grid_bounds(self, m, n):
+        """-> (lo [3], hi [3]) float64: the bounds of the vertices that the faces not left out reference; None when there are
+        none. A device reduction over plumbing tensors and ONE host read."""
+        if n == 0:
+            return None
+        V, F = self.vertex_buffer[:m], self.face_buffer[:n]
+        big = torch.full((3,), math.inf, dtype=torch.float32, device=self.device)
+        lo, hi = big.clone(), -big
+        for i in range(0, n, 1 << 20):                              # a million faces at a time: tens of megabytes, not hundreds
+            Fc = F[i:i + (1 << 20)].to(torch.int64)
+            ok = ((Fc >= 0) & (Fc < m)).all(dim=1)
+            P = V[Fc.clamp(0, m - 1)]                               # [c,3,3]
+            ok &= torch.isfinite(P).all(dim=2).all(dim=1)
+            lo = torch.minimum(lo, torch.where(ok[:, None, None], P, big).amin(dim=(0, 1)))
+            hi = torch.maximum(hi, torch.where(ok[:, None, None], P, -big).amax(dim=(0, 1)))
+        words = torch.cat([lo, hi]).to(torch.float64).tolist()      # ONE host read
+        if not all(math.isfinite(w) for w in words):
+            return None
+        return np.array(words[:3]), np.array(words[3:])
+
+    def face_grid(self, cell, origin=None, dims=None, capacity=None, _max_cells=None, _bounds=False):
+        """-> FaceGrid: a uniform grid of `cell` over the faces as a CSR table (the module's docstring and include/sfgs.h state
+        it). origin, dims: the grid's corner and its cell counts (nx, ny, nz), as a TSDF volume's; None for both: the bounds of
+        the referenced finite vertices, origin = their minimum and dims = floor((max - origin) / cell) + 1 per axis, by a device
+        reduction and one host read. capacity: the length of `pairs`; None sizes it by ONE host read of the pair total between
+        count and fill; an integer costs no read, and one too small is reported by FaceGrid.check().
+        _max_cells: private; a face whose range holds more cells goes to the large list (every value gives the same answers)."""
+        cell = _positive(cell, "cell")
+        if (origin is None) != (dims is None):
+            raise ValueError("origin and dims come together")
+        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or
+                                     not 0 <= capacity <= _INT32_MAX):
+            raise ValueError(f"capacity must be None or an integer in 0 ... 2^31 - 1, got {capacity!r}")
+        if _max_cells is not None and (isinstance(_max_cells, bool) or not isinstance(_max_cells, (int, np.integer)) or
+                                       not 0 <= _max_cells <= 1 << 30):
+            raise ValueError(f"_max_cells must be None or an integer in 0 ... 2^30, got {_max_cells!r}")
+        m, n = self._sizes()
+        if origin is None:
+            box = self._grid_bounds(m, n) if _bounds is False else _bounds       # _bounds: closest() has read them already
+            org, dims = grid_from_bounds(box, cell)
+        else:
+            org = _vec(origin, 3, "origin")
+            if not np.isfinite(org).all():
+                raise ValueError(f"origin must be finite, got {origin!r}")
+            try:
+                dims = tuple(int(d) for d in dims)
+            except (TypeError, ValueError):
+                raise ValueError(f"dims must be three integers, got {dims!r}") from None
+        if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] > MAX_GRID_CELLS:
+            raise ValueError(f"dims must be three integers >= 1 with at most 2^28 cells in all, got {dims!r}")
+        cells = dims[0] * dims[1] * dims[2]
+        dev, lib = self.device, L.load()
+        with torch.cuda.device(dev):
+            cell_start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+            large = torch.empty(n, dtype=torch.int32, device=dev)
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            args = L.SfgsMeshGrid(L.C.sizeof(L.SfgsMeshGrid), dims[0], dims[1], dims[2], (L.C.c_double * 3)(*[float(x) for x in org]),
+                                  cell, m, n, -1 if _max_cells is None else int(_max_cells), 0, self.vertex_buffer.data_ptr(),
+                                  self.face_buffer.data_ptr(), cell_start.data_ptr(), None, large.data_ptr(), state.data_ptr())
+            scratch = _call.scratch(lib.sfgs_mesh_grid_scratch_bytes(*dims), dev, refused_if_zero=True)
+            L.check(lib.sfgs_mesh_grid_count(L.C.byref(args), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+            if capacity is None:
+                total, _, status, _ = state.tolist()                # ONE host read
+                if status & _ST_PAIRS:
+                    raise ValueError(f"face_grid: {total} (face, cell) pairs, more than 2^31 - 1: use a larger cell")
+                capacity = total
+            pairs = torch.empty(int(capacity), dtype=torch.int32, device=dev)
+            args.capacity, args.pairs = int(capacity), pairs.data_ptr()
+            L.check(lib.sfgs_mesh_grid_fill(L.C.byref(args), L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+        return FaceGrid(self, cell, org, dims, cell_start, pairs, large, state, args)
+
+    def closest(self, points, grid=None, max_distance=None, closest_points=False, _max_cells=None):
+        """-> MeshDistance: for each point the closest face of the mesh and the squared distance to it, in float64 (the module's
+        docstring and include/sfgs.h state the answer; it does not depend on the grid). points: float32 or float64 [k,3] on the
+        mesh's device, contiguous. grid: a face_grid() result of THIS mesh, a cell size (a grid is built over the mesh's
+        bounds), or None: a grid with the cell default_cell() picks from the bounds and the face count. max_distance: an
+        answer farther away is reported as face -1 and sqdist +inf. closest_points: also the closest point, float32 [k,3]."""
+        _call.check_tensor("points", points, "[k,3]", lambda t: t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous(),
+                           dtypes=(torch.float32, torch.float64))
+        _call.check_gpu(points=points)
+        _call.same_device(self.device, "the mesh's device", points=points)
+        if max_distance is None:
+            max_distance = math.inf
+        if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)) or not max_distance >= 0:
+            raise ValueError(f"max_distance must be None or a number >= 0, got {max_distance!r}")
+        if isinstance(grid, FaceGrid):
+            if grid.mesh is not self:
+                raise ValueError("grid was made for another mesh")
+            if _max_cells is not None:
+                raise ValueError("_max_cells goes with a grid built here")
+        elif grid is None:
+            m, n = self._sizes()
+            box = self._grid_bounds(m, n)
+            grid = self.face_grid(default_cell(box, n), _max_cells=_max_cells, _bounds=box)
+        else:
+            grid = self.face_grid(grid, _max_cells=_max_cells)
+        k = int(points.shape[0])
+        dev, lib = self.device, L.load()
+        with torch.cuda.device(dev):
+            sqdist = torch.empty(k, dtype=torch.float64, device=dev)
+            face = torch.empty(k, dtype=torch.int32, device=dev)
+            point = torch.empty((k, 3), dtype=torch.float32, device=dev) if closest_points else None
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            L.check(lib.sfgs_mesh_closest(L.C.byref(grid._args), L.ptr(points.detach()), int(points.dtype == torch.float64), k,
+                                          float(max_distance), L.ptr(sqdist), L.ptr(face), L.ptr(point), L.ptr(state), _call.stream(dev)))
+        return MeshDistance(sqdist, face, point, state, grid)
+
+    def sample(self, density, seed=0, capacity=None, colors=True):
+        """-> MeshSamples: points on the surface, uniform per area, `density` per unit of area on average, the same bytes for the
+        same seed (the module's docstring and include/sfgs.h state them), ordered by face. capacity: the rows of the outputs; a
+        row beyond it is not written but still counted, as TsdfVolume.extract does; None counts first and costs ONE host read.
+        colors: also the interpolated colours when the mesh has them."""
+        if isinstance(density, bool) or not isinstance(density, (int, float, np.integer, np.floating)) or not np.isfinite(density) or \
+                density < 0:
+            raise ValueError(f"density must be a finite number >= 0, got {density!r}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 32:
+            raise ValueError(f"seed must be an integer in 0 ... 2^32 - 1, got {seed!r}")
+        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or
+                                     not 1 <= capacity <= _INT32_MAX):
+            raise ValueError(f"capacity must be None or an integer in 1 ... 2^31 - 1, got {capacity!r}")
+        m, n = self._sizes()
+        dev, lib = self.device, L.load()
+        with_colors = bool(colors) and self.color_buffer is not None
+        with torch.cuda.device(dev):
+            state = torch.empty(4, dtype=torch.int64, device=dev)
+            scratch = _call.scratch(lib.sfgs_mesh_sample_scratch_bytes(n), dev, refused_if_zero=True)
+
+            def run(cap, points, face, cols):
+                L.check(lib.sfgs_mesh_sample(L.ptr(self.vertex_buffer), L.ptr(self.color_buffer), L.ptr(self.face_buffer), m, n,
+                                             float(density), int(seed), cap, L.ptr(points), L.ptr(face), L.ptr(cols), L.ptr(state),
+                                             L.ptr(scratch), scratch.numel(), _call.stream(dev)))
+            if capacity is None:
+                run(0, None, None, None)                            # counts only
+                capacity, _, status, _ = state.tolist()             # ONE host read
+                _raise_query_status(status, "sample")
+            capacity = int(capacity)
+            points = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+            face = torch.empty(capacity, dtype=torch.int32, device=dev)
+            cols = torch.empty((capacity, 3), dtype=torch.float32, device=dev) if with_colors else None
+            if capacity > 0:
+                run(capacity, points, face, cols)
+        return MeshSamples(points, face, cols, state, capacity)
 
     def save_ply(self, path, origin=None, normals=None):
         """Binary little-endian PLY in TriangleSoup.save_ply's layout: a `vertex` and a `face` element (`property list uchar int
